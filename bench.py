@@ -4,8 +4,15 @@
 that reached host memory.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c3b|c5] [--deliver p6|f32]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what is
+reported beside the headline: the CPU baselines, the parity checks against the reference's
+outputs, the secondary measurements and the RCCL leg (--no-cpu-baseline, --no-parity,
+--no-extras and --no-rccl-leg leave one of them out of a --full run).  --dump-outputs DIR writes
+the frame the last timed step delivered as DIR/frame.npy.
 
 A step = one full frame delivered to rank 0's host memory, as the reference's timed region
 is render() plus the device-to-host copy of the frame (G/src/main.cu:369-376).  The native
@@ -18,13 +25,13 @@ processes (POSIX shm pinned in each, per-rank completion words; rank 0's wait re
 every rank has published the frame).  Frames are pipelined 2 deep on one GPU, 3 over N.
 Every timed frame is waited for in host memory before the clock stops.  At N > 1 the RCCL
 strip gather over xGMI (rank 0 assembles the frame in its HBM, then copies it) is measured
-after the headline and reported beside it (rccl_gather).
+after the headline and reported beside it (rccl_gather, with --full).
 --deliver f32 delivers the float framebuffer (the reference's own payload, 4x the bytes).
 --comm torch keeps the older torch.distributed gather (nccl or gloo) as an alternate launcher.
 A failed native multi-GPU path exits non-zero; --allow-fallback permits the gloo gather.
 
 Scene upload and BVH build are outside the timed region (as G/src/main.cu:362-378 times only
-render() + copy); the LBVH build times are reported beside (lbvh_build).  Rank 0 prints one
+render() + copy); the LBVH build times are reported beside with --full (lbvh_build).  Rank 0 prints one
 JSON line.
 """
 from __future__ import annotations
@@ -119,15 +126,52 @@ def parse():
     ap.add_argument("--hw-queues", type=int, default=HW1_HW_QUEUES,
                     help="c1 / c2: GPU_MAX_HW_QUEUES for this process (a delivery lane per 2; set before HIP "
                          "initialises)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what is reported beside it: the CPU baselines, the parity "
+                         "checks against the reference's outputs, the secondary measurements (render only, the "
+                         "other payload and submission mode, band shards, LBVH build, ray counts) and, at N > 1, "
+                         "the RCCL leg.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last timed step delivered to host memory "
+                         "as DIR/frame.npy (float32; a fixed seeded sample of a frame past the size cap)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity checks")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the secondary measurements")
     ap.add_argument("--tune", action="append", default=[], metavar="KNOB=VALUE",
                     help="library tuning knob (rt_tuning_set, include/rt_mi355x.h), e.g. peer_timeout_s=60; "
                          "named in the line's config when set")
     ap.add_argument("--traffic-file", default=str(REPO / "profiles" / "traffic.json"),
                     help="per-launch HBM bytes and issue counters measured by rocprofv3 --pmc (DESIGN.md §5)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:  # a plain run does only what its headline needs
+        a.no_cpu_baseline = a.no_parity = a.no_extras = a.no_rccl_leg = True
+    return a
+
+
+# ---- --dump-outputs ----------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # of .npy payload over all arrays
+DUMP_SEED = 20260315
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """Write what the timed path delivered in its last step as <out_dir>/<name>.npy, float32.
+    An array past its share of DUMP_MAX_BYTES is cut to a sample of its elements (flat indices
+    drawn once from DUMP_SEED, sorted), the same sample in every run of the same arguments."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    share = (DUMP_MAX_BYTES - 4096 * len(arrays)) // len(arrays)
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        x = x if x.dtype == np.float64 else x.astype(np.float32)
+        if x.nbytes > share:
+            idx = np.random.default_rng(DUMP_SEED).choice(x.size, share // x.itemsize, replace=False)
+            x = x.reshape(-1)[np.sort(idx)]
+        np.save(d / f"{name}.npy", x)
+
+
+def frame_array(body: bytes, deliver: str, W: int, H: int) -> np.ndarray:
+    """The delivered frame as an H x W x 3 array: P6 samples (uint8) or the float framebuffer."""
+    return np.frombuffer(body, np.uint8 if deliver == "p6" else np.float32).reshape(H, W, 3)
 
 
 # ---- CPU baseline -----------------------------------------------------------------------
@@ -787,6 +831,8 @@ def hw1_main(a):
     elapsed = time.perf_counter() - t0
     submit_ms = nxt["submit_s"] / a.steps * 1e3  # host time inside rt_render_hw1_deliver per frame
     last_host = host[(nxt["k"] - 1) % depth]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"frame": frame_array(last_host.numpy().tobytes(), "p6", W, H)})
     kms = sc.kernel_times(min(a.steps, 64))
     kernel_ms = float(np.median(kms))
     rays = W * H * spp
@@ -907,6 +953,8 @@ def main():
     if comm == "torch":
         a.deliver = a.gather_payload
         res = torch_path(a, hs, cam, cfg, world, rank, ctx.devices[0], ctx.dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"frame": frame_array(res["frame_bytes"], a.deliver, W, H)})
 
     elapsed = res["elapsed"]
     vals = [elapsed, res["kernel_ms"], res["frame_ms"]]

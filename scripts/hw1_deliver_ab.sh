@@ -11,7 +11,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for L in $LANES; do
     for E in $ENGINES; do
       f=$OUT/L${L}_E${E}.$r
-      timeout -k 10 200 python3 "$ROOT/bench.py" --config c2 --steps "${STEPS:-200}" --warmup 10 --no-cpu-baseline \
+      timeout -k 10 200 python3 "$ROOT/bench.py" --config c2 --steps "${STEPS:-200}" --warmup 10 --full --no-cpu-baseline \
           --tune hw1_lanes=$L --tune copy_engine=$E > "$f.json" 2> "$f.err" || exit 1
       echo "L$L E$E round $r $(python3 -c "import json; d=json.loads(open('$f.json').read().splitlines()[-1]); t=d['timing']; print(d['ms_per_step'], t['kernel_ms'], t.get('host_submit_ms_per_frame'), d['parity']['timed_step_ppm_identical'])")"
     done

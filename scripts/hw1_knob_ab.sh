@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 for r in $(seq 1 "$ROUNDS"); do
   for v in "$@"; do
     f=$OUT/${KNOB}_$v.$r
-    timeout -k 10 200 python3 "$ROOT/bench.py" --config "${CFG:-c2}" --steps "${STEPS:-200}" --warmup 10 --no-cpu-baseline \
+    timeout -k 10 200 python3 "$ROOT/bench.py" --config "${CFG:-c2}" --steps "${STEPS:-200}" --warmup 10 --full --no-cpu-baseline \
         --tune "$KNOB=$v" > "$f.json" 2> "$f.err" || exit 1
     echo "$KNOB=$v round $r $(python3 -c "import json; d=json.loads(open('$f.json').read().splitlines()[-1]); t=d['timing']; print(d['ms_per_step'], t['kernel_ms'], t.get('host_submit_ms_per_frame'), t.get('host_wait_ms_per_frame'), d['parity']['timed_step_ppm_identical'])")"
   done

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {  # name, rocprof args...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o run -- \
-      python3 "$ROOT/bench.py" --no-cpu-baseline --no-parity $ARGS > "$OUT/$name.log" 2>&1
+      python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-parity $ARGS > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "$name rc=$rc"
   if [ $rc -ge 124 ]; then exit $rc; fi

@@ -40,8 +40,30 @@ def test_torch_comm_needs_a_launcher():
         assert r.returncode != 0 and "needs one process per GPU" in r.stderr
 
 
+def test_dump_outputs_caps_the_bytes_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; an array past the cap is cut to the same seeded sample
+    of its elements in every run, a smaller one is written whole."""
+    import numpy as np
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1_000_000)
+    big = np.arange(300 * 400 * 3, dtype=np.uint32).reshape(300, 400, 3) % 251
+    small = np.linspace(0.0, 1.0, 12, dtype=np.float64).reshape(2, 2, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, {"frame": big.astype(np.uint8), "small": small})
+    a, b = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "b" / "frame.npy")
+    assert a.dtype == np.float32 and a.ndim == 1 and 100_000 < a.size < big.size
+    assert np.array_equal(a, b)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(big.size, a.size, replace=False))
+    assert np.array_equal(a, big.reshape(-1)[idx].astype(np.float32))
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 1_000_000
+
+
 def test_bench_help_lists_the_paths():
     r = _bench(["--help"])
     assert r.returncode == 0
-    for flag in ("--allow-fallback", "--share-gpu", "--gather", "--no-rccl-leg", "c3b"):
+    for flag in ("--allow-fallback", "--share-gpu", "--gather", "--no-rccl-leg", "c3b", "--full", "--dump-outputs"):
         assert flag in r.stdout

@@ -46,7 +46,9 @@ def _line(stdout: str) -> dict:
     return json.loads([ln for ln in stdout.splitlines() if ln.startswith("{")][-1])
 
 
-def _bench(args, nproc=None, timeout=420):
+def _bench(args, nproc=None, timeout=420, full=True):
+    """bench.py --full: the tests below read the parity checks and the secondary measurements."""
+    args = [*(["--full"] if full else []), *args]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     if nproc:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
@@ -74,6 +76,26 @@ def test_bench_in_process_one_gpu():
     assert line["n_gpus"] == 1 and line["value"] > 0
     assert "gather=direct" in line["config"]["comm"] and line["config"]["processes"] == 1
     assert line["parity"]["timed_step_ppm_identical"]
+
+
+def test_bench_plain_run_dumps_the_timed_frame(tmp_path):
+    """Without --full: the headline line alone (nothing that is measured beside it), --steps timed
+    steps, and --dump-outputs writes the last timed frame: c3's P6 samples, the reference's image."""
+    r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--preroll-ms", "0", "--dump-outputs", str(tmp_path)],
+               full=False)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _line(r.stdout)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["warmup_frames_run"] == 1
+    for moved in ("parity", "cpu_baseline", "parity_primary_hits", "rays_per_frame", "lbvh_build"):
+        assert moved not in line
+    assert "render_only_value" not in line["timing"] and "band_shards_one_gpu" not in line["timing"]
+    assert [p.name for p in tmp_path.iterdir()] == ["frame.npy"]
+    frame = np.load(tmp_path / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (H, W, 3)
+    ppm = gzip.open(GOLDEN / "scenes" / "c3_full" / "image.ppm.gz").read()
+    want = np.frombuffer(ppm[len(rt.p6_header(W, H)):], np.uint8).reshape(H, W, 3)
+    assert np.array_equal(frame, want.astype(np.float32))
 
 
 def test_bench_in_process_two_band_shards():
