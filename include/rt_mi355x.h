@@ -451,6 +451,51 @@ int rt_hw1_list_info(const rt_hw1_scene* s, int64_t info[2]);
 int rt_intersect_rays(int device, const rt_triangle* tri, const float origin[3], const float* dirs, int n,
                       int hw1, float tmin, float tmax, int32_t* hit, float* t);
 
+/* ---- batched ray queries on a resident scene ---------------------------------------------
+ * The reference's ray-level queries for caller rays against an rt_scene: one ray per GPU lane,
+ * each lane running the reference's DFS on its own.
+ *
+ * RT_RAYS_CLOSEST: SearchBVH(numTriangles, Ray(origin, direction), ...) exactly
+ *   (G/include/query.h:224-311): tmin = 1e-4 (:233), bestT = FLT_MAX, the direction used as given
+ *   (never normalised), a later-visited triangle with t <= bestT wins (query.h:72-108 through
+ *   :268-275), and on a tree that overflows the 512-entry stack (:245) the brute-force completion
+ *   over every triangle in index order decides (:298-308).  hit_idx[i] = the triangle index, or -1
+ *   on a miss; hit_t[i] = the reference's t bit for bit, or -1.0f on a miss (what
+ *   rt_intersect_rays writes); hit_t may be NULL.  max_t must be NULL (the reference has no such
+ *   bound): RT_ERR_ARG otherwise.
+ * RT_RAYS_OCCLUDED: the decision of IsInShadow (G/include/shader.h:59-61): hit_idx[i] = 1 iff
+ *   SearchBVH hits and t < max_t[i], else 0 (a NaN max_t[i] gives 0).  max_t is required and hit_t
+ *   must be NULL (RT_ERR_ARG otherwise): a lane may stop at the first accepted triangle with
+ *   t < max_t[i] (bestT only decreases after it, so the decision stands), and the closest t is
+ *   then not known.
+ * flags: RT_FLAG_BINARY traverses the binary records, not the 4-ary ones (same answers); any other
+ *   bit is RT_ERR_ARG.  n == 0 is RT_OK with no launch; n > 2^31-1 is RT_ERR_UNSUPPORTED.  A null
+ *   scene, rays or hit_idx is RT_ERR_ARG.  Every argument check runs before any HIP call.
+ * A query reads only the scene's immutable packed arrays and takes no part in the frame ordering
+ * of rt_render_device (none of its events, work buffers or frame counters): it may run on any
+ * stream, and from any thread, beside frames of the same scene, of a clone (rt_scene_clone) or of
+ * a scene owned by an rt_renderer (rt_renderer_scene).
+ * For any float bit patterns in rays and max_t the call terminates and writes every output (the
+ * DFS visits each node at most once whatever the comparisons say); the results are specified
+ * for finite rays only. */
+typedef struct { rt_vec3 origin, direction; } rt_ray;   /* layout = reference: Ray, G/include/ray.h:6-22 (24 B) */
+enum { RT_RAYS_CLOSEST = 0, RT_RAYS_OCCLUDED = 1 };
+enum { RT_RAYS_VARIANT_NONE = 0, RT_RAYS_VARIANT_WIDE = 1, RT_RAYS_VARIANT_BINARY = 2, RT_RAYS_VARIANT_DEEP = 3 };
+
+/* Asynchronous on hip_stream (NULL = the null stream); all pointers are device pointers on the
+ * scene's device: rays_dev n rt_ray, max_t_dev / hit_idx_dev / hit_t_dev n entries each. */
+int rt_trace_rays_device(rt_scene* s, int mode, const rt_ray* rays_dev, const float* max_t_dev, size_t n,
+                         int flags, int32_t* hit_idx_dev, float* hit_t_dev, void* hip_stream);
+/* Host arrays; uploads, traces, downloads, synchronises.  kernel_ms (may be NULL): HIP-event time
+ * of the kernel. */
+int rt_trace_rays(rt_scene* s, int mode, const rt_ray* rays, const float* max_t, size_t n, int flags,
+                  int32_t* hit_idx, float* hit_t, float* kernel_ms);
+/* Which traversal the latest rt_trace_rays[_device] call on s launched (RT_RAYS_VARIANT_*; NONE
+ * before the first): DEEP (SearchBVH as written, 512-entry private stack) for a scene that takes
+ * the deep kernels (rt_scene_traversal_info) or whose per-lane stack does not fit LDS, else WIDE
+ * (4-ary records, per-lane stack in LDS) or, with RT_FLAG_BINARY, BINARY. */
+int rt_trace_rays_variant(const rt_scene* s);
+
 /* The Blinn-Phong powf of the kernels (restatement of the reference libm's powf, see
  * csrc/rt_math.hpp): rt_powf_host evaluates the host build, rt_powf_batch the device build
  * over n (x, y) pairs.  Exposed so both can be pinned against the C library's powf. */

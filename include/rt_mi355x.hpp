@@ -128,6 +128,32 @@ inline Framebuffer render(const DeviceScene& ds, const Camera& cam, const rt_ren
     return fb;
 }
 
+// Batched ray queries against a resident scene (rt_trace_rays): SearchBVH per ray
+// (G/include/query.h:224-311), the direction used as given.
+struct RayHits {
+    std::vector<int32_t> tri;  // triangle index, -1 = miss
+    std::vector<float> t;      // the reference's t, -1 = miss
+};
+inline RayHits trace_closest(const DeviceScene& ds, const std::vector<rt_ray>& rays, int flags = 0) {
+    RayHits h;
+    h.tri.resize(rays.size());
+    h.t.resize(rays.size());
+    if (!rays.empty())
+        check(rt_trace_rays(ds.get(), RT_RAYS_CLOSEST, rays.data(), nullptr, rays.size(), flags, h.tri.data(),
+                            h.t.data(), nullptr));
+    return h;
+}
+// IsInShadow's decision (G/include/shader.h:59-61) per ray: 1 where a hit has t < max_t[i].
+inline std::vector<int32_t> trace_occluded(const DeviceScene& ds, const std::vector<rt_ray>& rays,
+                                           const std::vector<float>& max_t, int flags = 0) {
+    if (max_t.size() != rays.size()) throw Error(RT_ERR_ARG, "trace_occluded: one max_t per ray");
+    std::vector<int32_t> occ(rays.size());
+    if (!rays.empty())
+        check(rt_trace_rays(ds.get(), RT_RAYS_OCCLUDED, rays.data(), max_t.data(), rays.size(), flags, occ.data(),
+                            nullptr, nullptr));
+    return occ;
+}
+
 inline void write_p6(const std::string& path, const Framebuffer& fb, const rt_ppm_options* opt = nullptr) {
     check(rt_ppm_write(path.c_str(), fb.rgb.data(), fb.width, fb.height, opt));
 }

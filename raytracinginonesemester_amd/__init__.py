@@ -5,7 +5,8 @@ include/rt_mi355x.h); this package is the host-side mirror of the reference inte
 """
 from ._lib import (RTError, RT_DELIVER_DEVICE, RT_DELIVER_F32, RT_DELIVER_NONE, RT_DELIVER_P6,  # noqa: F401
                    RT_GATHER_AUTO, RT_GATHER_DIRECT, RT_GATHER_HOST_SHARED, RT_GATHER_RCCL, RT_KERNEL_AUTO, RT_KERNEL_LANE,
-                   RT_KERNEL_WAVE, RT_RENDERER_SELF_SEND, RT_TILES_AUTO, RT_TILES_LINEAR, RT_TILES_ROWS,
+                   RT_KERNEL_WAVE, RT_FLAG_BINARY, RT_RAYS_CLOSEST, RT_RAYS_OCCLUDED, RT_RAYS_VARIANT_BINARY,
+                   RT_RAYS_VARIANT_DEEP, RT_RAYS_VARIANT_NONE, RT_RAYS_VARIANT_WIDE, RT_RENDERER_SELF_SEND, RT_TILES_AUTO, RT_TILES_LINEAR, RT_TILES_ROWS,
                    RT_TILES_XCD_CHUNK, RT_TIME_DELIVER, RT_TIME_FRAME, RT_TIME_GATHER)
 from .api import (  # noqa: F401
     LIGHT_DTYPE, Camera, DeviceScene, HostScene, HW1Scene, MeshHW1, Renderer, build_bvh, comm_unique_id, build_bvh_device, default_material, device_count,

@@ -27,6 +27,8 @@ RT_GATHER_AUTO, RT_GATHER_RCCL, RT_GATHER_DIRECT, RT_GATHER_HOST_SHARED = 0, 1, 
 RT_RENDERER_SELF_SEND = 1
 RT_TIME_GATHER, RT_TIME_DELIVER, RT_TIME_FRAME = 0, 1, 2
 RT_FAULT_FRUSTUM_STACK = 1
+RT_RAYS_CLOSEST, RT_RAYS_OCCLUDED = 0, 1
+RT_RAYS_VARIANT_NONE, RT_RAYS_VARIANT_WIDE, RT_RAYS_VARIANT_BINARY, RT_RAYS_VARIANT_DEEP = 0, 1, 2, 3
 # rt_tune_id (include/rt_mi355x.h): knob name -> id
 TUNE = {"frustum_arity": 0, "half_waves": 1, "paired_only": 2, "heavy_frac": 3, "heavy_cap": 4,
         "cull_coverage": 5, "cull_boxes": 6, "big_scene_bytes": 7, "frustum_stack_cap": 8,
@@ -182,6 +184,9 @@ SIGNATURES = {
     "rt_hw1_kernel_name": (C.c_char_p, [P]),
     "rt_hw1_list_info": (I, [P, P]),
     "rt_intersect_rays": (I, [I, P, P, P, I, I, C.c_float, C.c_float, P, P]),
+    "rt_trace_rays_device": (I, [P, I, P, P, SZ, I, P, P, P]),
+    "rt_trace_rays": (I, [P, I, P, P, SZ, I, P, P, P]),
+    "rt_trace_rays_variant": (I, [P]),
     "rt_powf_host": (C.c_float, [C.c_float, C.c_float]),
     "rt_debug_frustum_records": (C.c_int, [C.c_size_t, P, P, C.c_int, C.c_int, P, P, C.c_size_t]),
     "rt_powf_batch": (I, [I, P, P, I, P]),

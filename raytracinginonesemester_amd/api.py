@@ -340,6 +340,69 @@ class DeviceScene:
         return {"frustum_log2": int(info[0]), "frustum_bound": int(info[1]), "wide": bool(info[2]),
                 "deep": bool(info[3])}
 
+    def trace_rays(self, rays, mode: str = "closest", max_t=None, flags: int = 0, stream: Optional[int] = None,
+                   timing: bool = False):
+        """Batched ray queries against this scene (rt_trace_rays / rt_trace_rays_device): ``rays`` is
+        (n, 6) float32, origin then direction, the direction used as given.
+
+        * ``mode="closest"``: SearchBVH (G/include/query.h:224-311) per ray; returns ``(idx, t)``,
+          int32 triangle indices (-1: miss) and the reference's float32 t (-1.0: miss).
+        * ``mode="occluded"``: IsInShadow's decision (G/include/shader.h:59-61) against ``max_t``
+          (n float32, required); returns a bool array, True where a hit has t < max_t.
+
+        A numpy array takes the host path (upload, trace, download, synchronise; ``timing=True``
+        appends the kernel's HIP-event ms).  Torch tensors on the scene's device take the device
+        path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no
+        host synchronisation, tensors returned.  ``flags``: RT_FLAG_BINARY or 0."""
+        modes = {"closest": L.RT_RAYS_CLOSEST, "occluded": L.RT_RAYS_OCCLUDED}
+        if mode not in modes:
+            raise ValueError(f"trace_rays: mode must be one of {sorted(modes)}, not {mode!r}")
+        m = modes[mode]
+        occluded = m == L.RT_RAYS_OCCLUDED
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
+                raise ValueError(f"trace_rays: expects an (n, 6) float32 tensor on {dev}")
+            if timing:
+                raise ValueError("trace_rays: timing is measured on the host path only")
+            rays = rays.contiguous()
+            n = rays.shape[0]
+            mt = None
+            if max_t is not None:
+                mt = torch.as_tensor(max_t, dtype=torch.float32, device=dev).contiguous()
+                if mt.shape != (n,):
+                    raise ValueError("trace_rays: max_t must hold one float per ray")
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            idx = torch.empty(n, dtype=torch.int32, device=dev)
+            t = None if occluded else torch.empty(n, dtype=torch.float32, device=dev)
+            check(lib().rt_trace_rays_device(self._handle(), m, rays.data_ptr(), None if mt is None else mt.data_ptr(),
+                                             n, int(flags), idx.data_ptr(), None if t is None else t.data_ptr(),
+                                             stream))
+            return idx != 0 if occluded else (idx, t)
+        r = _c(rays, np.float32)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("trace_rays: expects an (n, 6) array of origins and directions")
+        n = r.shape[0]
+        mt = None
+        if max_t is not None:
+            mt = _c(max_t, np.float32)
+            if mt.shape != (n,):
+                raise ValueError("trace_rays: max_t must hold one float per ray")
+        idx = np.zeros(n, np.int32)
+        t = None if occluded else np.zeros(n, np.float32)
+        ms = C.c_float(0.0)
+        check(lib().rt_trace_rays(self._handle(), m, ptr(r), ptr(mt), n, int(flags), ptr(idx), ptr(t),
+                                  C.byref(ms) if timing else None))
+        out = idx != 0 if occluded else (idx, t)
+        return (out, ms.value) if timing else out
+
+    def trace_rays_variant(self) -> int:
+        """The traversal the latest trace_rays call launched (RT_RAYS_VARIANT_*)."""
+        return int(lib().rt_trace_rays_variant(self._handle()))
+
     def faults(self, clear: bool = True) -> int:
         """RT_FAULT_* bits the device guards raised since the last clear (rt_scene_faults)."""
         f = C.c_uint32()

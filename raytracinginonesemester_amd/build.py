@@ -4,7 +4,7 @@
 
 * librt_mi355x.so — the host units rt_host.cpp and rt_records.cpp (g++) + the device translation
   units (hipcc --offload-arch=gfx950): rt_device.hip (scene + render; its device code in the
-  rt_wave/instrument/traverse/shade/prepass.hpp sections), rt_hw1.hip (the HW1 path),
+  rt_wave/instrument/traverse/shade/prepass/query.hpp sections), rt_hw1.hip (the HW1 path),
   rt_frame.hip (P6 quantisation and strip un-permute on the device), rt_lbvh.hip (LBVH build on
   the device), rt_renderer.hip (the multi-GPU frame renderer).  Units compile in parallel.
   Every float path is compiled with -ffp-contract=off and without fast-math; HIP's default

@@ -34,6 +34,7 @@
 //   rt_traverse.hpp    the traversals (wave DFS, frustum, lane, LDS, deep)
 //   rt_shade.hpp       hit resolution, materials, camera ray, shading, bounces, trace_sample
 //   rt_prepass.hpp     tile bounds, root and tree-cut culling passes, work lists
+//   rt_query.hpp       batched ray queries on a resident scene (rt_trace_rays*)
 // Separate translation units: rt_records.cpp (host record builders), rt_hw1.hip (the HW1 path),
 // rt_frame.hip, rt_lbvh.hip, rt_renderer.hip.
 
@@ -47,6 +48,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <functional>
 #include <memory>
 #include <new>
@@ -187,6 +189,7 @@ struct RenderParams {
 #include "rt_traverse.hpp"
 #include "rt_shade.hpp"
 #include "rt_prepass.hpp"
+#include "rt_query.hpp"
 
 // The render kernel's work: list q's entries, its heavy lists' first (classes in order,
 // heaviest first; each capped at heavy_cap), then its survivors (the cut pass's list, or the
@@ -617,6 +620,9 @@ using rt::DeviceGuard;
 struct rt_scene {
     int device = 0;
     const char* last_kernel = nullptr;  // the render kernel instantiation of the latest frame
+    // RT_RAYS_VARIANT_* of the latest rt_trace_rays[_device] call (queries run beside frames,
+    // from any thread: the one scene field they write)
+    std::atomic<int> query_variant{RT_RAYS_VARIANT_NONE};
     size_t P = 0;
     int nmat = 0, nlights = 0;
     uint32_t root_ref = 0;
@@ -1890,6 +1896,120 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     return rc;
 }
 }  // namespace
+
+// ---- batched ray queries (rt_query.hpp) ----------------------------------------------------
+namespace {
+// The argument checks of rt_trace_rays[_device]: no HIP call and no read through s before they
+// pass (a CPU-only host reaches every one of them).
+int trace_rays_args(const rt_scene* s, int mode, const void* rays, const float* max_t, size_t n, int flags,
+                    const int32_t* hit_idx, const float* hit_t) {
+    if (!s) return set_error(RT_ERR_ARG, "rt_trace_rays: null scene");
+    if (mode != RT_RAYS_CLOSEST && mode != RT_RAYS_OCCLUDED) return set_error(RT_ERR_ARG, "rt_trace_rays: unknown mode");
+    if (mode == RT_RAYS_CLOSEST && max_t) return set_error(RT_ERR_ARG, "rt_trace_rays: closest-hit queries take no max_t");
+    if (mode == RT_RAYS_OCCLUDED && !max_t) return set_error(RT_ERR_ARG, "rt_trace_rays: occlusion queries need max_t");
+    if (mode == RT_RAYS_OCCLUDED && hit_t) return set_error(RT_ERR_ARG, "rt_trace_rays: occlusion queries write no hit_t");
+    if (flags & ~RT_FLAG_BINARY) return set_error(RT_ERR_ARG, "rt_trace_rays: unknown flag");
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_trace_rays: more than 2^31-1 rays in one batch");
+    if (!rays || !hit_idx) return set_error(RT_ERR_ARG, "rt_trace_rays: null rays or hit_idx");
+    return RT_OK;
+}
+
+template <int VARIANT>
+void launch_query(const QueryParams& Q, bool any, hipStream_t st) {
+    const dim3 grid((Q.n + BLOCK - 1) / BLOCK), block(BLOCK);
+    if (any) hipLaunchKernelGGL((trace_rays_kernel<VARIANT, true>), grid, block, 0, st, Q);
+    else hipLaunchKernelGGL((trace_rays_kernel<VARIANT, false>), grid, block, 0, st, Q);
+}
+
+// One launch on st; nothing of the scene's frame state (events, work sets, launches) is touched.
+int trace_rays_launch(rt_scene* s, int mode, const rt_ray* rays, const float* max_t, size_t n, int flags,
+                      int32_t* hit_idx, float* hit_t, hipStream_t st) {
+    // The first that applies: DEEP for a deep scene; WIDE, else BINARY, where the per-lane stack
+    // of those records fits LDS; else DEEP, which is exact for any tree (a tree that is not deep
+    // needs at most STACK_CAP of its 512 entries, so the brute-force completion, and with it the
+    // absent tri array, is unreachable).
+    int variant = RT_RAYS_VARIANT_DEEP;
+    if (!s->deep) {
+        if (s->wide && s->lane_wide && !(flags & RT_FLAG_BINARY)) variant = RT_RAYS_VARIANT_WIDE;
+        else if (s->lane_stack) variant = RT_RAYS_VARIANT_BINARY;
+    }
+    if (s->deep && !s->tri.p) return set_error(RT_ERR_INTERNAL, "rt_trace_rays: a deep scene without its triangle array");
+    QueryParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.sc.inode = static_cast<const float4*>(s->inode.p);
+    Q.sc.wnode = static_cast<const float4*>(s->wnode.p);
+    Q.sc.ibox = static_cast<const float4*>(s->ibox.p);
+    Q.sc.rootb = static_cast<const float4*>(s->ibox.p) + s->ibox.n / sizeof(float4) - 2;
+    Q.sc.leaf = static_cast<const float4*>(s->leaf.p);
+    Q.sc.tri = static_cast<const float4*>(s->tri.p);
+    Q.sc.num_tris = int32_t(s->P);
+    Q.sc.root_ref = s->root_ref;
+    std::memcpy(Q.sc.root_box, s->root_box, sizeof(Q.sc.root_box));
+    std::memcpy(Q.sc.bmax, s->bmax, sizeof(Q.sc.bmax));
+    Q.sc.wide = variant == RT_RAYS_VARIANT_WIDE ? 1 : 0;
+    Q.sc.lane_stack = s->lane_stack ? 1 : 0;
+    Q.sc.lane_wide = s->lane_wide ? 1 : 0;
+    Q.sc.f_log2 = 2;
+    Q.rays = reinterpret_cast<const float*>(rays);
+    Q.max_t = max_t;
+    Q.n = uint32_t(n);
+    Q.hit_idx = hit_idx;
+    Q.hit_t = hit_t;
+    const bool any = mode == RT_RAYS_OCCLUDED;
+    if (variant == RT_RAYS_VARIANT_WIDE) launch_query<RT_RAYS_VARIANT_WIDE>(Q, any, st);
+    else if (variant == RT_RAYS_VARIANT_BINARY) launch_query<RT_RAYS_VARIANT_BINARY>(Q, any, st);
+    else launch_query<RT_RAYS_VARIANT_DEEP>(Q, any, st);
+    HIP_TRY(hipGetLastError());
+    s->query_variant.store(variant, std::memory_order_relaxed);
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_trace_rays_device(rt_scene* s, int mode, const rt_ray* rays, const float* max_t, size_t n, int flags,
+                                    int32_t* hit_idx, float* hit_t, void* stream) {
+    const int rc = trace_rays_args(s, mode, rays, max_t, n, flags, hit_idx, hit_t);
+    if (rc != RT_OK || n == 0) return rc;
+    DeviceGuard g(s->device);
+    return trace_rays_launch(s, mode, rays, max_t, n, flags, hit_idx, hit_t, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rt_trace_rays(rt_scene* s, int mode, const rt_ray* rays, const float* max_t, size_t n, int flags,
+                             int32_t* hit_idx, float* hit_t, float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.0f;
+    int rc = trace_rays_args(s, mode, rays, max_t, n, flags, hit_idx, hit_t);
+    if (rc != RT_OK || n == 0) return rc;
+    DeviceGuard g(s->device);
+    DevBuf dr, dm, di, dt;
+    if ((rc = dr.upload(rays, n * sizeof(rt_ray))) != RT_OK) return rc;
+    if (max_t && (rc = dm.upload(max_t, n * sizeof(float))) != RT_OK) return rc;
+    if ((rc = di.alloc(n * sizeof(int32_t))) != RT_OK) return rc;
+    if (hit_t && (rc = dt.alloc(n * sizeof(float))) != RT_OK) return rc;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } ev;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, nullptr));
+    }
+    rc = trace_rays_launch(s, mode, static_cast<const rt_ray*>(dr.p), static_cast<const float*>(dm.p), n, flags,
+                           static_cast<int32_t*>(di.p), static_cast<float*>(dt.p), nullptr);
+    if (rc != RT_OK) return rc;
+    if (kernel_ms) HIP_TRY(hipEventRecord(ev.b, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    HIP_TRY(hipMemcpy(hit_idx, di.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (hit_t) HIP_TRY(hipMemcpy(hit_t, dt.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_trace_rays_variant(const rt_scene* s) {
+    return s ? s->query_variant.load(std::memory_order_relaxed) : RT_RAYS_VARIANT_NONE;
+}
 
 void rt::scene_set_caller_ordered(rt_scene* s, bool on) {
     if (s) s->caller_ordered = on;
