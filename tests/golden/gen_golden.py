@@ -8,6 +8,7 @@ reference's own code: jitter tables, ray-triangle KAT answers, camera bases, sce
 
     python tests/golden/gen_golden.py            # all fixtures
     python tests/golden/gen_golden.py --only c3_small
+    python tests/golden/gen_golden.py --only 'shade_*'
 """
 from __future__ import annotations
 
@@ -181,6 +182,44 @@ def gen_chain(name: str) -> None:
         (dst / "meta.json").write_text(json.dumps(meta, indent=1) + "\n")
 
 
+# AOVs of these shading cases (64 and 128 spp) are kept by sha256 only
+SHADE_AOV_MAX_SPP = 16
+
+
+def shade_cases() -> dict:
+    sys.path.insert(0, str(HERE.parent))
+    import shade_fuzz
+
+    return {"shade_" + n: n for n in shade_fuzz.CASES}
+
+
+def gen_shade(name: str) -> None:
+    """A shading fuzz case (tests/shade_fuzz.py: random material tables, object ids and light
+    sets) through the reference render() and SearchBVH (ref_g arrays, miss colour 0)."""
+    sys.path.insert(0, str(HERE.parent))
+    import shade_fuzz
+
+    c = shade_fuzz.case(name)
+    dst = HERE / "scenes" / ("shade_" + name)
+    dst.mkdir(parents=True, exist_ok=True)
+    with tempfile.TemporaryDirectory() as td:
+        t = Path(td)
+        shade_fuzz.write_arrays(c, t)
+        run([REF / "ref_g", "arrays", t, t, c["W"], c["H"], c["spp"], c["depth"], 1 if c["diffuse"] else 0])
+        meta = json.loads((t / "meta.json").read_text())
+        meta["generator"] = "tests/shade_fuzz.py case(%r)" % name
+        meta["num_materials"] = int(c["mats"].size)
+        meta["sha256"] = {k: sha256(t / k) for k in (*shade_fuzz.INPUTS, "fb.f32", "hits.i32", "hitt.f32")}
+        assert {k: meta["sha256"][k] for k in shade_fuzz.INPUTS} == shade_fuzz.input_sha256(c)
+        gz(t / "fb.f32", dst / "fb.f32.gz")
+        for k in ("hits.i32", "hitt.f32"):
+            if c["spp"] <= SHADE_AOV_MAX_SPP:
+                gz(t / k, dst / (k + ".gz"))
+            elif (dst / (k + ".gz")).exists():
+                (dst / (k + ".gz")).unlink()
+        (dst / "meta.json").write_text(json.dumps(meta, indent=1) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*")
@@ -194,6 +233,11 @@ def main() -> None:
     for n in chain_bvh.FIXTURES:
         if not want or n in want:
             gen_chain(n)
+    import fnmatch
+
+    for full, n in shade_cases().items():
+        if not want or any(fnmatch.fnmatchcase(full, w) for w in want):
+            gen_shade(n)
     if not want or "jitter" in want:
         gen_jitter()
     if not want or "kat" in want:
