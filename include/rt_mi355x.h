@@ -519,6 +519,15 @@ int rt_box_test_host(const float* rays, const float* boxes, const float* tminmax
 int rt_debug_frustum_records(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, int max_log2, int stack_cap,
                              int64_t* info, float* rec, size_t rec_cap);
 
+/* Host half of rt_scene_create (no device): the arrays it would upload for this BVH, digested.
+ * info = {P, root ref, cut boxes, log2 sub-boxes per cut box, wide, lane_stack, lane_wide, deep,
+ * frustum log2 arity, frustum stack bound, binary DFS stack bound, 4-ary DFS stack bound, then
+ * the float bit patterns of the root box (min, max corner) and of bmax}; digests = per array
+ * (inode, wnode, fnode, qent, qhdr, ibox, leaf, tnorm, cut, cut2, tri) its byte length and the
+ * 64-bit FNV-1a hash of its bytes.  Errors as rt_scene_create reports them for these arrays. */
+int rt_debug_scene_pack(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                        int64_t info[21], uint64_t digests[22]);
+
 /* Durations (ms) of the render kernel of the most recent min(max, launches, 256) timed
  * rt_render_device calls on this scene, oldest first, measured with HIP events recorded
  * on the launch stream around the kernel (direct calls are all timed; an rt_renderer's frames

@@ -2,9 +2,11 @@
 
     python -m raytracinginonesemester_amd.build
 
-* librt_mi355x.so — the host units rt_host.cpp and rt_records.cpp (g++) + the device translation
-  units (hipcc --offload-arch=gfx950): rt_device.hip (scene + render; its device code in the
-  rt_wave/instrument/traverse/shade/prepass/query.hpp sections), rt_hw1.hip (the HW1 path),
+* librt_mi355x.so — the host units rt_host.cpp, rt_records.cpp and rt_scene_pack.cpp (g++; the
+  last is rt_scene_create's host half: checks, ids, stack bounds and every packed array) + the
+  device translation units (hipcc --offload-arch=gfx950): rt_device.hip (scene upload + render;
+  its device code in the rt_wave/instrument/traverse/shade/prepass/query.hpp sections),
+  rt_hw1.hip (the HW1 path),
   rt_frame.hip (P6 quantisation and strip un-permute on the device), rt_lbvh.hip (LBVH build on
   the device), rt_renderer.hip (the multi-GPU frame renderer).  Units compile in parallel.
   Every float path is compiled with -ffp-contract=off and without fast-math; HIP's default
@@ -37,7 +39,7 @@ HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
 FP = ["-ffp-contract=off", "-fno-fast-math"]
 DEVICE_UNITS = ["rt_device", "rt_hw1", "rt_frame", "rt_lbvh", "rt_renderer"]
-HOST_UNITS = ["rt_host", "rt_records"]
+HOST_UNITS = ["rt_host", "rt_records", "rt_scene_pack"]
 
 
 ID_TAG = b"RT_BUILD_ID:"

@@ -6,7 +6,7 @@
 // TraceRayIterative query.h:156-220, SearchBVH query.h:224-311, ShadeDirect/IsInShadow
 // shader.h:44-110, EvaluateBRDF brdf.h:12-40, Camera::get_ray camera.h:49-53.
 //
-// Device layout (built from the reference arrays by rt_scene_create):
+// Device layout (built from the reference arrays by rt::pack_scene, rt_scene_pack.cpp):
 //   inode[i]  64 B  children's AABBs + child refs of internal node i   (4 x float4)
 //   ibox[i]   32 B  internal node i's own AABB (pop-time re-tests)      (2 x float4)
 //   leaf[j]   64 B  v0, e1, e2, triangle index and the leaf's own AABB  (4 x float4)
@@ -35,8 +35,9 @@
 //   rt_shade.hpp       hit resolution, materials, camera ray, shading, bounces, trace_sample
 //   rt_prepass.hpp     tile bounds, root and tree-cut culling passes, work lists
 //   rt_query.hpp       batched ray queries on a resident scene (rt_trace_rays*)
-// Separate translation units: rt_records.cpp (host record builders), rt_hw1.hip (the HW1 path),
-// rt_frame.hip, rt_lbvh.hip, rt_renderer.hip.
+// Separate translation units: rt_scene_pack.cpp (the host half of rt_scene_create: checks, ids,
+// stack bounds, every packed array), rt_records.cpp (host record builders), rt_hw1.hip (the HW1
+// path), rt_frame.hip, rt_lbvh.hip, rt_renderer.hip.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -60,20 +61,21 @@
 #include "rt_hip_host.hpp"
 #include "rt_math.hpp"
 #include "rt_ppm.hpp"
-#include "rt_records.hpp"
+#include "rt_scene_pack.hpp"
 
 using namespace rtd;
 
 namespace {
 
-constexpr uint32_t LEAF_BIT = 0x80000000u;
-constexpr uint32_t NO_REF = 0xFFFFFFFFu;
-// traverse_frustum's stack: two VGPRs, entry k in lane k of the first, 64 + k of the second
-constexpr int FRUSTUM_STACK = 128;
+// the constants the packed layout shares with its host builders (rt_records.hpp)
+using rt::LEAF_BIT;
+using rt::NO_REF;
+using rt::FRUSTUM_STACK;
+using rt::STACK_CAP;
+using rt::LANE_LDS_CAP;
+using rt::kBigSceneBytes;
 constexpr uint32_t RT_FAULT_FRUSTUM_STACK = 1u;  // rt_scene_faults bit 0
 constexpr uint32_t VER_FORCE = 0xFFFFFFFFu;   // pop must re-test (root)
-constexpr int STACK_CAP = 64;                 // one entry per lane of the wave stack
-constexpr int LANE_LDS_CAP = 32;              // traverse_lane_lds: per-lane stack entries in LDS (frog needs 18)
 constexpr int BLOCK = 256;
 // Kernel instantiation flag on top of RT_KERNEL_WAVE: traverse the 4-ary records (SceneView::wide).
 // A compile-time choice, so each kernel holds one traversal loop per ray kind.
@@ -388,7 +390,6 @@ __device__ __forceinline__ void pixels_tile(const RenderParams& P, int tile, uin
 #ifndef RT_RENDER_WAVES_BIG
 #define RT_RENDER_WAVES_BIG 8
 #endif
-constexpr size_t kBigSceneBytes = size_t(64) << 20;
 // Two frames in one launch (RT_TUNE_PAIR_FRAMES, rt_renderer_submit_pair): frame A's parameters,
 // then frame B's, one kernel argument.
 struct PairParams {
@@ -608,41 +609,23 @@ __global__ __launch_bounds__(BLOCK) void intersect_kernel(f3 v0, f3 e1, f3 e2, f
 // =========================================================================================
 using rt::set_error;
 using rt::hip_msg;
-using rt::FrustumRecords;
-using rt::build_frustum_records;
-using rt::build_quant_records;
-using rt::subtree_leaves;
-static_assert(LEAF_BIT == rt::kRecLeafBit && NO_REF == rt::kRecNoRef, "record ids follow the kernels' refs");
 using rt::DevBuf;
 using rt::check_device;
 using rt::DeviceGuard;
 
-struct rt_scene {
+struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hpp), then its device state
     int device = 0;
     const char* last_kernel = nullptr;  // the render kernel instantiation of the latest frame
     // RT_RAYS_VARIANT_* of the latest rt_trace_rays[_device] call (queries run beside frames,
     // from any thread: the one scene field they write)
     std::atomic<int> query_variant{RT_RAYS_VARIANT_NONE};
-    size_t P = 0;
-    int nmat = 0, nlights = 0;
-    uint32_t root_ref = 0;
-    float root_box[6] = {0, 0, 0, 0, 0, 0};
-    float bmax[3] = {0, 0, 0};
     DevBuf inode, wnode, ibox, leaf, tnorm, objids, mats, lights, jitter;
     DevBuf fnode;    // 2^f_log2-ary records of the frustum traversal (empty: it takes wnode's 4-ary ones)
-    int f_log2 = 2;
-    int f_bound = 0;  // their DFS stack bound (<= FRUSTUM_STACK unless RT_TUNE_FRUSTUM_STACK_CAP raised it)
     DevBuf qent, qhdr;  // fnode quantised (build_quant_records): the big-scene kernels' records
     DevBuf fault;     // one word: RT_FAULT_* bits the kernels OR in (rt_scene_faults)
     DevBuf cut;  // tile culling: boxes of a cut of the tree (6 floats each)
-    int ncut = 0;
     DevBuf cut2;  // 2^cut_sub_log2 boxes below each cut box (tile_cut_sub), 6 floats each
-    int cut_sub_log2 = 0;
-    bool deep = false;  // the DFS may need more than STACK_CAP entries: MODE_DEEP kernels
     DevBuf tri;         // deep: triangles by index (brute-force completion)
-    bool wide = false;
-    bool lane_stack = false;  // binary DFS stack <= LANE_LDS_CAP (traverse_lane_lds)
-    bool lane_wide = false;   // 4-ary records whose DFS stack <= LANE_LDS_CAP (traverse_lane_lds_wide)
     DevBuf work;  // kSets counter sets, then kSets x (live lists | cut survivor lists | heavy lists)
     int64_t last_tiles_total = 0;
     int cus = 256;
@@ -746,397 +729,88 @@ extern "C" int rt_device_count(int* n) {
     return RT_OK;
 }
 
-// The frustum and 4-ary record builders are host code of their own (rt_records.cpp).
+// Scene creation is pack (rt::pack_scene, host code of its own: rt_scene_pack.cpp) -> upload.
+// The scene's device arrays, once: rt::PackedScene::arrays() in its order, then the caller's
+// tables.  rt_scene_create uploads them, rt_scene_clone copies them, `bytes` sums the counted.
+namespace {
+struct SceneBuf {
+    DevBuf rt_scene::*buf;
+    bool counted;  // part of rt_scene_device_bytes
+};
+constexpr SceneBuf kSceneBufs[] = {
+    {&rt_scene::inode, true}, {&rt_scene::wnode, true}, {&rt_scene::fnode, true}, {&rt_scene::qent, false},
+    {&rt_scene::qhdr, false}, {&rt_scene::ibox, true},  {&rt_scene::leaf, true},  {&rt_scene::tnorm, true},
+    {&rt_scene::cut, false},  {&rt_scene::cut2, false}, {&rt_scene::tri, false},
+    {&rt_scene::objids, true}, {&rt_scene::mats, true}, {&rt_scene::lights, true}};
+static_assert(sizeof(kSceneBufs) / sizeof(kSceneBufs[0]) == rt::PackedScene::kArrays + 3, "packed arrays + objids, mats, lights");
+
+// What the kernels read of a resident scene; the launches then set what depends on the frame
+// or the query (wide, ncut, f_log2).
+SceneView scene_view(const rt_scene* s) {
+    SceneView v;
+    std::memset(&v, 0, sizeof(v));
+    v.inode = static_cast<const float4*>(s->inode.p);
+    v.wnode = static_cast<const float4*>(s->wnode.p);
+    v.fnode = static_cast<const float*>(s->fnode.p);
+    v.f_log2 = s->fnode.p ? s->f_log2 : 2;
+    v.qent = static_cast<const uint4*>(s->qent.p);
+    v.qhdr = static_cast<const float4*>(s->qhdr.p);
+    v.ibox = static_cast<const float4*>(s->ibox.p);
+    v.rootb = static_cast<const float4*>(s->ibox.p) + s->ibox.n / sizeof(float4) - 2;
+    v.leaf = static_cast<const float4*>(s->leaf.p);
+    v.tnorm = static_cast<const float4*>(s->tnorm.p);
+    v.objids = static_cast<const int32_t*>(s->objids.p);
+    v.mats = static_cast<const DevMaterial*>(s->mats.p);
+    v.lights = static_cast<const DevLight*>(s->lights.p);
+    v.num_tris = int32_t(s->P);
+    v.num_mats = s->nmat;
+    v.num_lights = s->nlights;
+    v.root_ref = s->root_ref;
+    std::memcpy(v.root_box, s->root_box, sizeof(v.root_box));
+    std::memcpy(v.bmax, s->bmax, sizeof(v.bmax));
+    v.wide = s->wide ? 1 : 0;
+    v.lane_stack = s->lane_stack ? 1 : 0;
+    v.lane_wide = s->lane_wide ? 1 : 0;
+    v.cut = static_cast<const float*>(s->cut.p);
+    v.ncut = s->ncut;
+    v.cut2 = static_cast<const float*>(s->cut2.p);
+    v.cut_sub_log2 = s->cut2.p ? s->cut_sub_log2 : 0;
+    v.tri = static_cast<const float4*>(s->tri.p);
+    v.fault = static_cast<uint32_t*>(s->fault.p);
+    return v;
+}
+}  // namespace
 
 extern "C" int rt_scene_create(int device, size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs,
                                const rt_triangle* tris, const int32_t* objids, const rt_material* mats,
                                int nmat, const rt_light* lights, int nlights, rt_scene** out) {
     if (!out) return set_error(RT_ERR_ARG, "rt_scene_create: null out");
     *out = nullptr;
-    if (P == 0 || !nodes || !aabbs || !tris) return set_error(RT_ERR_ARG, "rt_scene_create: empty scene");
-    if (P > 0x3FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^30 triangles");
+    int rc = rt::check_scene_arrays(P, nodes, aabbs, tris);
+    if (rc != RT_OK) return rc;
     if (nmat < 0 || nlights < 0 || (nmat > 0 && !mats) || (nlights > 0 && !lights))
         return set_error(RT_ERR_ARG, "rt_scene_create: bad material/light arrays");
-    const size_t NN = 2 * P - 1;
-    // Classify nodes, give internal/leaf nodes compact ids, and check the reachable graph is
-    // a finite tree; a tree whose DFS may need more than the 64-entry wave stack (SearchBVH's
-    // push/pop order) is rendered by the MODE_DEEP kernels (the reference's 512-entry stack).
-    std::vector<uint32_t> cid(NN, NO_REF);
-    size_t n_int = 0, n_leaf = 0;
-    for (size_t n = 0; n < NN; ++n) {
-        const rt_bvh_node& nd = nodes[n];
-        if (nd.object_idx == 0xFFFFFFFFu) {
-            if ((nd.left_idx != NO_REF && nd.left_idx >= NN) || (nd.right_idx != NO_REF && nd.right_idx >= NN))
-                return set_error(RT_ERR_ARG, "BVH child index out of range");
-            cid[n] = uint32_t(n_int++);
-        } else if (nd.object_idx < P) {
-            cid[n] = LEAF_BIT | uint32_t(n_leaf++);
-        }  // leaves naming no valid triangle are skipped by SearchBVH (query.h:263): NO_REF
-    }
-    // Wide (4-ary) records: internal node n lists the children of its children in SearchBVH's
-    // push order (a leaf child stands for itself), so one visit tests and pushes what the
-    // reference reaches in two.  The result is the same provided every internal child's box
-    // contains its children's boxes (the pass the skipped test would give is then implied,
-    // slab tests being monotone in the box), checked here; the wave path falls back to the
-    // binary records otherwise, or when the 4-ary DFS stack would exceed 64 entries.
-    auto ref_of0 = [&](uint32_t n) -> uint32_t { return n == NO_REF ? NO_REF : cid[n]; };
-    // RT_TUNE_WIDE4_GREEDY (default 1): the 4-ary records' entries grown from the node's children
-    // by expanding, in place, the internal entry of largest surface area (up to 4 entries); 0:
-    // the grandchildren.  Exact for the reasons the grandchildren are (every box contains its
-    // children's, checked below for every parent-child pair; the DFS order is SearchBVH's; no
-    // leaf is tested between an expanded node's pop and its children's in the reference).
-    // c3 0.1390 vs 0.1419 ms, c3b 1.2455 vs 1.2986, c5 40.35 vs 40.82
-    // (profiles/r05/exp/wide4_greedy_ab.log)
-    const int wide4_rule = int(rt::tuning(RT_TUNE_WIDE4_GREEDY, 1.0) + 0.5);
-    const bool wide4_greedy = wide4_rule > 0;
-    const std::vector<uint32_t> wleaves = wide4_rule == 2 ? subtree_leaves(nodes, NN, cid.data()) : std::vector<uint32_t>();
-    auto box_area = [&](uint32_t n) {
-        const rt_aabb& b = aabbs[n];
-        const double dx = std::max(0.0, double(b.max_corner.x) - b.min_corner.x);
-        const double dy = std::max(0.0, double(b.max_corner.y) - b.min_corner.y);
-        const double dz = std::max(0.0, double(b.max_corner.z) - b.min_corner.z);
-        double a = dx * dy + dy * dz + dz * dx;
-        if (wide4_rule == 2) a *= std::sqrt(double(wleaves[n]));
-        return std::isfinite(a) ? a : 1e300;
-    };
-    auto wide_entries = [&](const rt_bvh_node& nd, uint32_t* e) {
-        int k = 0;
-        if (wide4_greedy) {
-            for (const uint32_t c : {nd.left_idx, nd.right_idx})
-                if (ref_of0(c) != NO_REF) e[k++] = c;
-            while (k < 4) {
-                int best = -1;
-                double ba = -1.0;
-                for (int i = 0; i < k; ++i) {
-                    if (ref_of0(e[i]) & LEAF_BIT) continue;
-                    const double a = box_area(e[i]);
-                    if (a > ba) {
-                        ba = a;
-                        best = i;
-                    }
-                }
-                if (best < 0) break;
-                uint32_t kids[2];
-                int nk = 0;
-                for (const uint32_t g : {nodes[e[best]].left_idx, nodes[e[best]].right_idx})
-                    if (ref_of0(g) != NO_REF) kids[nk++] = g;
-                uint32_t grown[4];
-                int t = 0;
-                for (int i = 0; i < k; ++i) {
-                    if (i != best) grown[t++] = e[i];
-                    else
-                        for (int j = 0; j < nk; ++j) grown[t++] = kids[j];
-                }
-                for (int i = 0; i < t; ++i) e[i] = grown[i];
-                k = t;
-            }
-            return k;
-        }
-        for (const uint32_t c : {nd.left_idx, nd.right_idx}) {
-            if (ref_of0(c) == NO_REF) continue;
-            if (ref_of0(c) & LEAF_BIT) {
-                e[k++] = c;
-                continue;
-            }
-            const rt_bvh_node& cn = nodes[c];
-            if (ref_of0(cn.left_idx) != NO_REF) e[k++] = cn.left_idx;
-            if (ref_of0(cn.right_idx) != NO_REF) e[k++] = cn.right_idx;
-        }
-        return k;
-    };
-    auto contains = [](const rt_aabb& o, const rt_aabb& i) {
-        return o.min_corner.x <= i.min_corner.x && o.min_corner.y <= i.min_corner.y &&
-               o.min_corner.z <= i.min_corner.z && o.max_corner.x >= i.max_corner.x &&
-               o.max_corner.y >= i.max_corner.y && o.max_corner.z >= i.max_corner.z;
-    };
-    bool wide_ok = true, deep = false;
-    int binary_stack = 0, wide_stack = 0;
-    {
-        std::vector<uint8_t> state(NN, 0);  // 0 new, 1 on path, 2 done
-        std::vector<int> S(NN, 0), SW(NN, 0);
-        std::vector<std::pair<uint32_t, bool>> st{{0u, false}};
-        while (!st.empty()) {
-            auto [v, post] = st.back();
-            st.pop_back();
-            const rt_bvh_node& nd = nodes[v];
-            const bool internal = nd.object_idx == 0xFFFFFFFFu;
-            if (!post) {
-                if (state[v] == 1) return set_error(RT_ERR_ARG, "BVH contains a cycle");
-                if (state[v] == 2) continue;
-                state[v] = 1;
-                st.push_back({v, true});
-                if (internal) {
-                    if (nd.left_idx != NO_REF) st.push_back({nd.left_idx, false});
-                    if (nd.right_idx != NO_REF) st.push_back({nd.right_idx, false});
-                }
-            } else {
-                state[v] = 2;
-                if (internal) {
-                    const int sl = nd.left_idx != NO_REF ? S[nd.left_idx] : 0;
-                    const int sr = nd.right_idx != NO_REF ? S[nd.right_idx] : 0;
-                    const int pushes = (nd.left_idx != NO_REF) + (nd.right_idx != NO_REF);
-                    int s = pushes;
-                    if (nd.right_idx != NO_REF) s = std::max(s, (nd.left_idx != NO_REF ? 1 : 0) + sr);
-                    if (nd.left_idx != NO_REF) s = std::max(s, sl);
-                    S[v] = s;
-                    for (const uint32_t c : {nd.left_idx, nd.right_idx}) {
-                        if (c == NO_REF || nodes[c].object_idx != 0xFFFFFFFFu) continue;
-                        for (const uint32_t g : {nodes[c].left_idx, nodes[c].right_idx})
-                            if (g != NO_REF && !contains(aabbs[c], aabbs[g])) wide_ok = false;
-                    }
-                    uint32_t e[4];
-                    const int k = wide_entries(nd, e);
-                    int sw = k;
-                    for (int i = 0; i < k; ++i)
-                        if (!(ref_of0(e[i]) & LEAF_BIT)) sw = std::max(sw, i + SW[e[i]]);
-                    SW[v] = sw;
-                }
-            }
-        }
-        deep = std::max(1, S[0]) > STACK_CAP;
-        binary_stack = std::max(1, S[0]);
-        wide_stack = std::max(1, SW[0]);
-        // traverse_wave_split addresses records by 32-bit byte offsets (ref << 7 into the 4-ary
-        // array, << 5 into ibox, slot << 6 into the leaves): larger trees take the MODE_DEEP
-        // kernels, which are exact for any tree.
-        if (n_int >= (size_t(1) << 25) || n_leaf >= (size_t(1) << 26)) deep = true;
-        if (deep || std::max(1, SW[0]) > STACK_CAP) wide_ok = false;
-    }
-    std::vector<float4> hin(4 * std::max<size_t>(n_int, 1)), hib(2 * std::max<size_t>(n_int, 1));
-    std::vector<float4> hwn(wide_ok ? 8 * std::max<size_t>(n_int, 1) : 0);
-    std::vector<float4> hlf(4 * std::max<size_t>(n_leaf, 1)), hnm(3 * P);
-    auto ref_of = [&](uint32_t n) -> uint32_t { return n == NO_REF ? NO_REF : cid[n]; };
-    for (size_t n = 0; n < NN; ++n) {
-        const uint32_t c = cid[n];
-        if (c == NO_REF) continue;
-        const rt_bvh_node& nd = nodes[n];
-        if (!(c & LEAF_BIT)) {
-            const rt_aabb lb = nd.left_idx != NO_REF ? aabbs[nd.left_idx] : rt_aabb{};
-            const rt_aabb rb = nd.right_idx != NO_REF ? aabbs[nd.right_idx] : rt_aabb{};
-            float4* q = &hin[4 * c];  // per axis (min, max) pairs: left x y | left z, right x | right y z
-            q[0] = make_float4(lb.min_corner.x, lb.max_corner.x, lb.min_corner.y, lb.max_corner.y);
-            q[1] = make_float4(lb.min_corner.z, lb.max_corner.z, rb.min_corner.x, rb.max_corner.x);
-            q[2] = make_float4(rb.min_corner.y, rb.max_corner.y, rb.min_corner.z, rb.max_corner.z);
-            // z: children that are leaves naming no triangle (pushed by SearchBVH all the same:
-            // the deep kernels keep their stack entries)
-            const uint32_t inv = (nd.left_idx != NO_REF && ref_of(nd.left_idx) == NO_REF ? 1u : 0u) |
-                                 (nd.right_idx != NO_REF && ref_of(nd.right_idx) == NO_REF ? 2u : 0u);
-            uint32_t refs[4] = {ref_of(nd.left_idx), ref_of(nd.right_idx), inv, 0u};
-            std::memcpy(&q[3], refs, 16);
-            const rt_aabb& ob = aabbs[n];
-            hib[2 * c] = make_float4(ob.min_corner.x, ob.max_corner.x, ob.min_corner.y, ob.max_corner.y);
-            hib[2 * c + 1] = make_float4(ob.min_corner.z, ob.max_corner.z, 0.f, 0.f);
-            if (wide_ok) {  // 4 x (x pair, y pair, z pair) | 4 refs | unused
-                float w[32] = {};
-                uint32_t e[4], wr[4] = {NO_REF, NO_REF, NO_REF, NO_REF};
-                const int k = wide_entries(nd, e);
-                for (int i = 0; i < k; ++i) {
-                    const rt_aabb& bb = aabbs[e[i]];
-                    const float v6[6] = {bb.min_corner.x, bb.max_corner.x, bb.min_corner.y,
-                                         bb.max_corner.y, bb.min_corner.z, bb.max_corner.z};
-                    std::memcpy(&w[6 * i], v6, sizeof(v6));
-                    wr[i] = ref_of(e[i]);
-                }
-                std::memcpy(&w[24], wr, sizeof(wr));
-                std::memcpy(&hwn[8 * c], w, sizeof(w));
-            }
-        } else {
-            const uint32_t j = c & ~LEAF_BIT;
-            const rt_triangle& t = tris[nd.object_idx];
-            const rt_aabb& ob = aabbs[n];
-            float4* q = &hlf[4 * j];
-            int32_t ti = int32_t(nd.object_idx);
-            float tif;
-            std::memcpy(&tif, &ti, 4);
-            // e1 = v1 - v0, e2 = v2 - v0 exactly as intersectTriangle computes them
-            // v0 | e1, e2.x | e2.y e2.z, box x pair | box y pair, box z pair
-            q[0] = make_float4(t.v0.x, t.v0.y, t.v0.z, tif);
-            q[1] = make_float4(t.v1.x - t.v0.x, t.v1.y - t.v0.y, t.v1.z - t.v0.z, t.v2.x - t.v0.x);
-            q[2] = make_float4(t.v2.y - t.v0.y, t.v2.z - t.v0.z, ob.min_corner.x, ob.max_corner.x);
-            q[3] = make_float4(ob.min_corner.y, ob.max_corner.y, ob.min_corner.z, ob.max_corner.z);
-        }
-    }
-    for (size_t t = 0; t < P; ++t) {
-        hnm[3 * t] = make_float4(tris[t].n0.x, tris[t].n0.y, tris[t].n0.z, 0.f);
-        hnm[3 * t + 1] = make_float4(tris[t].n1.x, tris[t].n1.y, tris[t].n1.z, 0.f);
-        hnm[3 * t + 2] = make_float4(tris[t].n2.x, tris[t].n2.y, tris[t].n2.z, 0.f);
-    }
-    int rc = check_device(device);
-    if (rc != RT_OK) return rc;
+    rt::PackedScene pk;
+    if ((rc = rt::pack_scene(P, nodes, aabbs, tris, pk)) != RT_OK) return rc;
+    if ((rc = check_device(device)) != RT_OK) return rc;
     DeviceGuard g(device);
     std::unique_ptr<rt_scene> s(new (std::nothrow) rt_scene());
     if (!s) return set_error(RT_ERR_NOMEM, "out of memory");
+    static_cast<rt::SceneMeta&>(*s) = pk.meta;
     s->device = device;
-    s->P = P;
     s->nmat = nmat;
     s->nlights = nlights;
-    s->root_ref = cid[0];
-    if (s->root_ref == NO_REF) s->root_ref = LEAF_BIT | 0u;  // degenerate: unreachable leaf
-    for (size_t n = 0; n < NN; ++n) {
-        const rt_aabb& bb = aabbs[n];
-        s->bmax[0] = std::max({s->bmax[0], std::fabs(bb.min_corner.x), std::fabs(bb.max_corner.x)});
-        s->bmax[1] = std::max({s->bmax[1], std::fabs(bb.min_corner.y), std::fabs(bb.max_corner.y)});
-        s->bmax[2] = std::max({s->bmax[2], std::fabs(bb.min_corner.z), std::fabs(bb.max_corner.z)});
+    size_t i = 0;
+    for (const rt::PackedArray& a : pk.arrays()) {
+        DevBuf& b = (*s).*kSceneBufs[i++].buf;
+        if (a.bytes && (rc = b.upload(a.data, a.bytes)) != RT_OK) return rc;
     }
-    // The pre-classification takes min <= max per axis (near/far bounds by the ray's sign); a
-    // scene with an inverted, NaN or infinite box gets bmax = inf, which turns every float
-    // classification ambiguous (make_ray: E = inf), so all its box tests take the exact path.
-    bool sorted_boxes = true;
-    for (size_t n = 0; n < NN; ++n) {
-        const rt_aabb& bb = aabbs[n];
-        sorted_boxes = sorted_boxes && bb.min_corner.x <= bb.max_corner.x && bb.min_corner.y <= bb.max_corner.y &&
-                       bb.min_corner.z <= bb.max_corner.z;
-    }
-    for (float& v : s->bmax)
-        if (!(v <= FLT_MAX) || !sorted_boxes) v = INFINITY;
-    s->root_box[0] = aabbs[0].min_corner.x; s->root_box[1] = aabbs[0].min_corner.y; s->root_box[2] = aabbs[0].min_corner.z;
-    s->root_box[3] = aabbs[0].max_corner.x; s->root_box[4] = aabbs[0].max_corner.y; s->root_box[5] = aabbs[0].max_corner.z;
-    if (cid[0] == NO_REF) {  // root names no triangle: nothing can be hit; empty box
-        s->root_box[0] = s->root_box[1] = s->root_box[2] = INFINITY;
-        s->root_box[3] = s->root_box[4] = s->root_box[5] = -INFINITY;
-    }
-    // Tile-culling cut (tile_misses_scene): from the root, repeatedly replace the internal node
-    // with the largest box (half surface area) by its children, up to kCut nodes.  Every leaf
-    // keeps exactly one ancestor-or-self in the set; a missing child (NO_REF) holds no leaf.
-    if (cid[0] != NO_REF && !(cid[0] & LEAF_BIT)) {
-        // one box per lane of tile_cut_kernel (RT_TUNE_CULL_BOXES: fewer, for tests)
-        const int kcut = int(std::clamp(rt::tuning(RT_TUNE_CULL_BOXES, 64.0), 0.0, 64.0));
-        auto area = [&](uint32_t n) {
-            const rt_aabb& bb = aabbs[n];
-            const double dx = double(bb.max_corner.x) - bb.min_corner.x, dy = double(bb.max_corner.y) - bb.min_corner.y,
-                         dz = double(bb.max_corner.z) - bb.min_corner.z;
-            const double a = dx * dy + dy * dz + dz * dx;
-            return a == a ? a : INFINITY;
-        };
-        std::vector<uint32_t> cutn{0u};
-        while (int(cutn.size()) < kcut) {
-            int best = -1;
-            double ba = -1.0;
-            for (int i = 0; i < int(cutn.size()); ++i) {
-                if (cid[cutn[i]] & LEAF_BIT) continue;
-                const double a = area(cutn[i]);
-                if (a > ba) { ba = a; best = i; }
-            }
-            if (best < 0) break;
-            const rt_bvh_node& nd = nodes[cutn[best]];
-            cutn.erase(cutn.begin() + best);
-            if (nd.left_idx != NO_REF && cid[nd.left_idx] != NO_REF) cutn.push_back(nd.left_idx);
-            if (nd.right_idx != NO_REF && cid[nd.right_idx] != NO_REF) cutn.push_back(nd.right_idx);
-        }
-        if (kcut > 1) {
-            std::vector<float> hc(6 * cutn.size());
-            for (size_t i = 0; i < cutn.size(); ++i) {
-                const rt_aabb& bb = aabbs[cutn[i]];
-                const float v6[6] = {bb.min_corner.x, bb.min_corner.y, bb.min_corner.z,
-                                     bb.max_corner.x, bb.max_corner.y, bb.max_corner.z};
-                std::memcpy(&hc[6 * i], v6, sizeof(v6));
-            }
-            if ((rc = s->cut.upload(hc.data(), hc.size() * sizeof(float))) != RT_OK) return rc;
-            s->ncut = int(cutn.size());
-            // Second level (RT_TUNE_CUT_SUB sub-boxes per cut box, a power of two <= 64): the
-            // same rule inside each cut node's subtree, so the tiles whose rays reach a cut box
-            // are tested against the boxes below it (tile_cut_sub).  Unused slots repeat the
-            // node's first sub-box: a duplicate changes no "every box missed" decision.
-            const int sub = int(std::clamp(rt::tuning(RT_TUNE_CUT_SUB, 16.0), 0.0, 64.0));
-            int sl = 0;
-            while ((2 << sl) <= sub) ++sl;
-            if (sub >= 2) {
-                const int S = 1 << sl;
-                std::vector<float> h2(size_t(6) * S * cutn.size());
-                for (size_t i = 0; i < cutn.size(); ++i) {
-                    std::vector<uint32_t> sn{cutn[i]};
-                    while (int(sn.size()) < S) {
-                        int best = -1;
-                        double ba = -1.0;
-                        for (int j = 0; j < int(sn.size()); ++j) {
-                            if (cid[sn[j]] & LEAF_BIT) continue;
-                            const double a = area(sn[j]);
-                            if (a > ba) { ba = a; best = j; }
-                        }
-                        if (best < 0) break;
-                        const rt_bvh_node& nd = nodes[sn[best]];
-                        std::vector<uint32_t> kids;
-                        if (nd.left_idx != NO_REF && cid[nd.left_idx] != NO_REF) kids.push_back(nd.left_idx);
-                        if (nd.right_idx != NO_REF && cid[nd.right_idx] != NO_REF) kids.push_back(nd.right_idx);
-                        if (int(sn.size()) - 1 + int(kids.size()) > S) break;
-                        sn.erase(sn.begin() + best);
-                        sn.insert(sn.end(), kids.begin(), kids.end());
-                        if (sn.empty()) break;
-                    }
-                    if (sn.empty()) sn.push_back(cutn[i]);
-                    for (int j = 0; j < S; ++j) {
-                        const rt_aabb& bb = aabbs[sn[size_t(j) < sn.size() ? j : 0]];
-                        const float v6[6] = {bb.min_corner.x, bb.min_corner.y, bb.min_corner.z,
-                                             bb.max_corner.x, bb.max_corner.y, bb.max_corner.z};
-                        std::memcpy(&h2[6 * (i * S + j)], v6, sizeof(v6));
-                    }
-                }
-                if ((rc = s->cut2.upload(h2.data(), h2.size() * sizeof(float))) != RT_OK) return rc;
-                s->cut_sub_log2 = sl;
-            }
-        }
-    }
-    if ((rc = s->inode.upload(hin.data(), hin.size() * sizeof(float4))) != RT_OK) return rc;
-    if (wide_ok && (rc = s->wnode.upload(hwn.data(), hwn.size() * sizeof(float4))) != RT_OK) return rc;
-    // the camera rays' frustum records (build_frustum_records), for the traversal's 128-entry stack
-    // RT_TUNE_FRUSTUM_ARITY: the largest arity's log2 to try (tests; 2 = the 4-ary records)
-    int fr_dmax = int(std::clamp(rt::tuning(RT_TUNE_FRUSTUM_ARITY, 5.0), 2.0, 5.0));
-#ifdef RT_NO_F16  // (variant builds for A/B runs: the frustum traversal over the 4-ary records)
-    fr_dmax = 2;
-#endif
-    const bool frustum = wide_ok && !(s->root_ref & LEAF_BIT) && fr_dmax > 2;
-    if (frustum) {
-        // RT_TUNE_FRUSTUM_STACK_CAP (test hook only): records whose DFS may outgrow the stack,
-        // to exercise traverse_frustum's overflow guard
-        const int cap = int(std::clamp(rt::tuning(RT_TUNE_FRUSTUM_STACK_CAP, double(FRUSTUM_STACK)), 1.0, 1e6));
-        const FrustumRecords fr = build_frustum_records(nodes, NN, cid.data(), aabbs, fr_dmax, cap);
-        if (fr.log2 > 2) {
-            if ((rc = s->fnode.upload(fr.rec.data(), fr.rec.size() * sizeof(float))) != RT_OK) return rc;
-            s->f_log2 = fr.log2;
-            s->f_bound = fr.bound;
-            // RT_TUNE_QUANT_RECORDS: 1 quantised records for every scene with frustum records,
-            // -1 for scenes whose float records alone exceed the big-scene threshold's eighth
-            // (c5: 34 MB; frog: 0.6 MB), 0 (default) none: c5 45.5 vs 42.4 ms with them, the
-            // dequantisation's VALU costing more than the halved record lines save
-            // (profiles/r05/exp/quant_records_ab_c5.log)
-            const double qk = rt::tuning(RT_TUNE_QUANT_RECORDS, 0.0);
-            const double big = rt::tuning(RT_TUNE_BIG_SCENE_BYTES, double(kBigSceneBytes));
-            const bool want_q = qk > 0.5 || (qk < -0.5 && double(fr.rec.size() * sizeof(float)) > big / 8.0);
-            std::vector<uint32_t> qe;
-            std::vector<float> qh;
-            if (want_q && build_quant_records(fr, qe, qh)) {
-                if ((rc = s->qent.upload(qe.data(), qe.size() * sizeof(uint32_t))) != RT_OK) return rc;
-                if ((rc = s->qhdr.upload(qh.data(), qh.size() * sizeof(float))) != RT_OK) return rc;
-            }
-        }
-    }
-    s->wide = wide_ok && !(s->root_ref & LEAF_BIT);
-    s->lane_stack = !deep && binary_stack <= LANE_LDS_CAP;
-    s->lane_wide = s->wide && s->lane_stack && wide_stack <= LANE_LDS_CAP;
-    s->deep = deep;
-    if (deep) {  // v0 | e1, e2.x | e2.y, e2.z by triangle index, e1/e2 as intersectTriangle computes them
-        std::vector<float4> ht(3 * P);
-        for (size_t t = 0; t < P; ++t) {
-            const rt_triangle& tr = tris[t];
-            ht[3 * t] = make_float4(tr.v0.x, tr.v0.y, tr.v0.z, 0.f);
-            ht[3 * t + 1] = make_float4(tr.v1.x - tr.v0.x, tr.v1.y - tr.v0.y, tr.v1.z - tr.v0.z, tr.v2.x - tr.v0.x);
-            ht[3 * t + 2] = make_float4(tr.v2.y - tr.v0.y, tr.v2.z - tr.v0.z, 0.f, 0.f);
-        }
-        if ((rc = s->tri.upload(ht.data(), ht.size() * sizeof(float4))) != RT_OK) return rc;
-    }
-    // the root's box (pair layout) after the internal boxes: the traversals' first test reads it
-    // with scalar loads like any other box (SceneView::rootb)
-    hib.push_back(make_float4(s->root_box[0], s->root_box[3], s->root_box[1], s->root_box[4]));
-    hib.push_back(make_float4(s->root_box[2], s->root_box[5], 0.f, 0.f));
-    if ((rc = s->ibox.upload(hib.data(), hib.size() * sizeof(float4))) != RT_OK) return rc;
-    if ((rc = s->leaf.upload(hlf.data(), hlf.size() * sizeof(float4))) != RT_OK) return rc;
-    if ((rc = s->tnorm.upload(hnm.data(), hnm.size() * sizeof(float4))) != RT_OK) return rc;
     if (objids && (rc = s->objids.upload(objids, P * sizeof(int32_t))) != RT_OK) return rc;
     if (nmat > 0 && (rc = s->mats.upload(mats, size_t(nmat) * sizeof(rt_material))) != RT_OK) return rc;
     if (nlights > 0 && (rc = s->lights.upload(lights, size_t(nlights) * sizeof(rt_light))) != RT_OK) return rc;
     if ((rc = s->create_sync()) != RT_OK) return rc;
-    s->bytes = s->inode.n + s->wnode.n + s->fnode.n + s->ibox.n + s->leaf.n + s->tnorm.n + s->objids.n +
-               s->mats.n + s->lights.n;
+    for (const SceneBuf& b : kSceneBufs)
+        if (b.counted) s->bytes += ((*s).*b.buf).n;
     *out = s.release();
     return RT_OK;
 }
@@ -1149,35 +823,16 @@ extern "C" int rt_scene_clone(const rt_scene* src, int device, rt_scene** out) {
     DeviceGuard g(device);
     std::unique_ptr<rt_scene> s(new (std::nothrow) rt_scene());
     if (!s) return set_error(RT_ERR_NOMEM, "out of memory");
+    static_cast<rt::SceneMeta&>(*s) = *src;
     s->device = device;
-    s->P = src->P;
-    s->nmat = src->nmat;
-    s->nlights = src->nlights;
-    s->root_ref = src->root_ref;
-    std::memcpy(s->root_box, src->root_box, sizeof(s->root_box));
-    std::memcpy(s->bmax, src->bmax, sizeof(s->bmax));
-    s->ncut = src->ncut;
-    s->cut_sub_log2 = src->cut_sub_log2;
-    s->wide = src->wide;
-    s->lane_stack = src->lane_stack;
-    s->lane_wide = src->lane_wide;
-    s->f_log2 = src->f_log2;
-    s->f_bound = src->f_bound;
-    s->deep = src->deep;
     s->cus = src->cus;
     s->bytes = src->bytes;
     // device-to-device copies of the packed arrays (over xGMI when the devices differ)
-    const std::pair<DevBuf*, const DevBuf*> bufs[] = {{&s->inode, &src->inode}, {&s->wnode, &src->wnode},
-                                                      {&s->fnode, &src->fnode},
-                                                      {&s->qent, &src->qent},   {&s->qhdr, &src->qhdr},
-                                                      {&s->ibox, &src->ibox},   {&s->leaf, &src->leaf},
-                                                      {&s->tnorm, &src->tnorm}, {&s->objids, &src->objids},
-                                                      {&s->mats, &src->mats},   {&s->lights, &src->lights},
-                                                      {&s->cut, &src->cut},     {&s->cut2, &src->cut2},
-                                                      {&s->tri, &src->tri}};
-    for (const auto& [d, q] : bufs) {
-        if ((rc = d->alloc(q->n)) != RT_OK) return rc;
-        if (q->n) HIP_TRY(hipMemcpyPeer(d->p, device, q->p, src->device, q->n));
+    for (const SceneBuf& b : kSceneBufs) {
+        DevBuf& d = (*s).*b.buf;
+        const DevBuf& q = (*src).*b.buf;
+        if ((rc = d.alloc(q.n)) != RT_OK) return rc;
+        if (q.n) HIP_TRY(hipMemcpyPeer(d.p, device, q.p, src->device, q.n));
     }
     if ((rc = s->create_sync()) != RT_OK) return rc;
     *out = s.release();
@@ -1530,37 +1185,12 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
 
     RenderParams P;
     std::memset(&P, 0, sizeof(P));
-    P.sc.inode = static_cast<const float4*>(s->inode.p);
-    P.sc.wnode = static_cast<const float4*>(s->wnode.p);
-    P.sc.fnode = static_cast<const float*>(s->fnode.p);
-    P.sc.f_log2 = s->fnode.p ? s->f_log2 : 2;
-    P.sc.qent = static_cast<const uint4*>(s->qent.p);
-    P.sc.qhdr = static_cast<const float4*>(s->qhdr.p);
-    P.sc.wide = s->wide && !(o->flags & RT_FLAG_BINARY) ? 1 : 0;
-    P.sc.lane_stack = s->lane_stack ? 1 : 0;
-    P.sc.lane_wide = s->lane_wide ? 1 : 0;
-    P.sc.ibox = static_cast<const float4*>(s->ibox.p);
-    P.sc.rootb = static_cast<const float4*>(s->ibox.p) + s->ibox.n / sizeof(float4) - 2;
-    P.sc.leaf = static_cast<const float4*>(s->leaf.p);
-    P.sc.tnorm = static_cast<const float4*>(s->tnorm.p);
-    P.sc.objids = static_cast<const int32_t*>(s->objids.p);
-    P.sc.mats = static_cast<const DevMaterial*>(s->mats.p);
-    P.sc.lights = static_cast<const DevLight*>(s->lights.p);
-    P.sc.num_tris = int32_t(s->P);
-    P.sc.num_mats = s->nmat;
-    P.sc.num_lights = s->nlights;
-    P.sc.root_ref = s->root_ref;
-    std::memcpy(P.sc.root_box, s->root_box, sizeof(P.sc.root_box));
-    P.sc.cut = static_cast<const float*>(s->cut.p);
-    P.sc.cut2 = static_cast<const float*>(s->cut2.p);
-    P.sc.cut_sub_log2 = s->cut2.p ? s->cut_sub_log2 : 0;
-    P.sc.tri = static_cast<const float4*>(s->tri.p);
-    P.sc.fault = static_cast<uint32_t*>(s->fault.p);
+    P.sc = scene_view(s);
+    if (o->flags & RT_FLAG_BINARY) P.sc.wide = 0;
     // RT_TUNE_CULL_COVERAGE: tests force the cut pass on (>= 1: always, untested candidates none)
     const double max_cov = rt::tuning(RT_TUNE_CULL_COVERAGE, 0.3);
-    P.sc.ncut = s->ncut > 0 && root_box_coverage(s->root_box, cam) <= max_cov ? s->ncut : 0;
+    if (P.sc.ncut > 0 && !(root_box_coverage(s->root_box, cam) <= max_cov)) P.sc.ncut = 0;
     P.cut_force = max_cov >= 1.0 ? 1 : 0;
-    std::memcpy(P.sc.bmax, s->bmax, sizeof(P.sc.bmax));
     P.cam_center = f3{cam->center.x, cam->center.y, cam->center.z};
     P.cam_p00 = f3{cam->pixel00_loc.x, cam->pixel00_loc.y, cam->pixel00_loc.z};
     P.cam_du = f3{cam->pixel_delta_u.x, cam->pixel_delta_u.y, cam->pixel_delta_u.z};
@@ -1936,20 +1566,10 @@ int trace_rays_launch(rt_scene* s, int mode, const rt_ray* rays, const float* ma
     if (s->deep && !s->tri.p) return set_error(RT_ERR_INTERNAL, "rt_trace_rays: a deep scene without its triangle array");
     QueryParams Q;
     std::memset(&Q, 0, sizeof(Q));
-    Q.sc.inode = static_cast<const float4*>(s->inode.p);
-    Q.sc.wnode = static_cast<const float4*>(s->wnode.p);
-    Q.sc.ibox = static_cast<const float4*>(s->ibox.p);
-    Q.sc.rootb = static_cast<const float4*>(s->ibox.p) + s->ibox.n / sizeof(float4) - 2;
-    Q.sc.leaf = static_cast<const float4*>(s->leaf.p);
-    Q.sc.tri = static_cast<const float4*>(s->tri.p);
-    Q.sc.num_tris = int32_t(s->P);
-    Q.sc.root_ref = s->root_ref;
-    std::memcpy(Q.sc.root_box, s->root_box, sizeof(Q.sc.root_box));
-    std::memcpy(Q.sc.bmax, s->bmax, sizeof(Q.sc.bmax));
+    Q.sc = scene_view(s);  // (the query kernels read none of the shading, frustum and cut arrays)
     Q.sc.wide = variant == RT_RAYS_VARIANT_WIDE ? 1 : 0;
-    Q.sc.lane_stack = s->lane_stack ? 1 : 0;
-    Q.sc.lane_wide = s->lane_wide ? 1 : 0;
     Q.sc.f_log2 = 2;
+    Q.sc.ncut = 0;
     Q.rays = reinterpret_cast<const float*>(rays);
     Q.max_t = max_t;
     Q.n = uint32_t(n);

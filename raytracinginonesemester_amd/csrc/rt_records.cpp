@@ -13,10 +13,6 @@
 #include "rt_common.hpp"
 
 namespace rt {
-namespace {
-constexpr uint32_t LEAF_BIT = kRecLeafBit;
-constexpr uint32_t NO_REF = kRecNoRef;
-}  // namespace
 
 // Wide records for the camera rays' frustum traversal (traverse_frustum): an internal node's
 // descendants D levels down in SearchBVH's push order, for the root and, in turn, every internal
@@ -27,11 +23,11 @@ constexpr uint32_t NO_REF = kRecNoRef;
 // wide_ok).  The largest A in {32, 16, 8} (at most 2^dmax) whose DFS needs at most `cap` stack
 // entries (FRUSTUM_STACK = 128: frog 32, bound 91; the c5 heightfield 32, bound 126); log2 = 2
 // when none fits (the frustum traversal then takes the 4-ary records, wnode).
-// cid: compact ids as rt_scene_create makes them (LEAF_BIT | slot, internal index, or NO_REF).
+// cid: compact ids as rt::classify_nodes makes them (LEAF_BIT | slot, internal index, or NO_REF).
 // (Leaf-pair entries, an internal node with two leaf children tested in one pop, measured no
 // faster: c3 0.1517 vs 0.1517 ms, c5 48.2 vs 45.9; profiles/r04/exp/pairs_stack128_ab_*.log.)
 // Valid leaves under each node (the greedy record rules' weights): a post-order walk from the
-// root over the nodes rt_scene_create gave ids (cid: NO_REF for nodes naming no valid triangle).
+// root over the nodes that have ids (cid: NO_REF for nodes naming no valid triangle).
 std::vector<uint32_t> subtree_leaves(const rt_bvh_node* nodes, size_t NN, const uint32_t* cid) {
     std::vector<uint32_t> leaves(NN, 0u);
     std::vector<uint8_t> seen(NN, 0);  // each node expanded once (the tree is checked elsewhere)
@@ -61,8 +57,19 @@ std::vector<uint32_t> subtree_leaves(const rt_bvh_node* nodes, size_t NN, const 
     return leaves;
 }
 
+double box_weight(const rt_aabb& b, int rule, uint32_t leaves) {
+    const double dx = std::max(0.0, double(b.max_corner.x) - b.min_corner.x);
+    const double dy = std::max(0.0, double(b.max_corner.y) - b.min_corner.y);
+    const double dz = std::max(0.0, double(b.max_corner.z) - b.min_corner.z);
+    double a = dx * dy + dy * dz + dz * dx;
+    if (rule == 2) a *= std::sqrt(double(leaves));
+    if (rule == 3) a *= std::log2(double(leaves) + 1.0);
+    if (rule == 4) a *= double(leaves);
+    return std::isfinite(a) ? a : 1e300;
+}
+
 FrustumRecords build_frustum_records(const rt_bvh_node* nodes, size_t NN, const uint32_t* cid,
-                                            const rt_aabb* aabbs, int dmax, int cap) {
+                                     const rt_aabb* aabbs, int dmax, int cap) {
     FrustumRecords out;
     auto ref_of0 = [&](uint32_t n) -> uint32_t { return n == NO_REF ? NO_REF : cid[n]; };
     // RT_TUNE_RECORD_GREEDY: a record's entries are grown from its node's children by expanding,
@@ -75,17 +82,7 @@ FrustumRecords build_frustum_records(const rt_bvh_node* nodes, size_t NN, const 
     const int greedy_rule = int(rt::tuning(RT_TUNE_RECORD_GREEDY, 2.0) + 0.5);
     const bool greedy = greedy_rule > 0;
     const std::vector<uint32_t> leaves = greedy_rule >= 2 ? subtree_leaves(nodes, NN, cid) : std::vector<uint32_t>();
-    auto area = [&](uint32_t n) {
-        const rt_aabb& b = aabbs[n];
-        const double dx = std::max(0.0, double(b.max_corner.x) - b.min_corner.x);
-        const double dy = std::max(0.0, double(b.max_corner.y) - b.min_corner.y);
-        const double dz = std::max(0.0, double(b.max_corner.z) - b.min_corner.z);
-        double a = dx * dy + dy * dz + dz * dx;
-        if (greedy_rule == 2) a *= std::sqrt(double(leaves[n]));
-        if (greedy_rule == 3) a *= std::log2(double(leaves[n]) + 1.0);
-        if (greedy_rule == 4) a *= double(leaves[n]);
-        return std::isfinite(a) ? a : 1e300;
-    };
+    auto area = [&](uint32_t n) { return box_weight(aabbs[n], greedy_rule, greedy_rule >= 2 ? leaves[n] : 0u); };
     for (int D = std::min(dmax, 5); D >= 3; --D) {
         const int A = 1 << D;
         auto expand = [&](auto&& self, uint32_t n, int d, uint32_t* e, int& k) -> void {
@@ -106,28 +103,9 @@ FrustumRecords build_frustum_records(const rt_bvh_node* nodes, size_t NN, const 
             std::array<uint32_t, 32> e;
             int k = 0;
             if (greedy) {
-                std::vector<uint32_t> fr;
                 for (uint32_t c : {nodes[recs[r]].left_idx, nodes[recs[r]].right_idx})
-                    if (ref_of0(c) != NO_REF) fr.push_back(c);
-                while ((int)fr.size() < A) {
-                    int best = -1;
-                    double ba = -1.0;
-                    for (int i = 0; i < (int)fr.size(); ++i) {
-                        if (ref_of0(fr[i]) & LEAF_BIT) continue;
-                        const double a = area(fr[i]);
-                        if (a > ba) {
-                            ba = a;
-                            best = i;
-                        }
-                    }
-                    if (best < 0) break;
-                    std::vector<uint32_t> kids;
-                    for (uint32_t c : {nodes[fr[best]].left_idx, nodes[fr[best]].right_idx})
-                        if (ref_of0(c) != NO_REF) kids.push_back(c);
-                    fr.erase(fr.begin() + best);
-                    fr.insert(fr.begin() + best, kids.begin(), kids.end());
-                }
-                for (uint32_t n : fr) e[k++] = n;
+                    if (ref_of0(c) != NO_REF) e[k++] = c;
+                k = expand_largest(nodes, cid, e.data(), k, A, true, area);
             } else {
                 expand(expand, nodes[recs[r]].left_idx, D - 1, e.data(), k);
                 expand(expand, nodes[recs[r]].right_idx, D - 1, e.data(), k);
@@ -230,60 +208,3 @@ bool build_quant_records(const FrustumRecords& fr, std::vector<uint32_t>& qent, 
 }
 
 }  // namespace rt
-
-using rt::set_error;
-using rt::kRecLeafBit;
-using rt::kRecNoRef;
-
-// Host-only view of build_frustum_records for the CPU tests (no device), with the ids as
-// rt_scene_create makes them.  info: log2, bound, record count.  rec: copied when rec_cap
-// (floats) suffices.
-extern "C" int rt_debug_frustum_records(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, int max_log2,
-                                        int stack_cap, int64_t* info, float* rec, size_t rec_cap) {
-    if (P == 0 || !nodes || !aabbs || !info) return set_error(RT_ERR_ARG, "rt_debug_frustum_records: null argument");
-    if (P > 0x3FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^30 triangles");
-    const size_t NN = 2 * P - 1;
-    // the caller's arrays are checked as rt_scene_create checks them: children in range and no
-    // cycle reachable from the root (tests/test_host_fuzz.py)
-    {
-        std::vector<uint8_t> state(NN, 0);  // 0 new, 1 on the path, 2 done
-        std::vector<std::pair<uint32_t, bool>> st{{0u, false}};
-        while (!st.empty()) {
-            auto [v, post] = st.back();
-            st.pop_back();
-            if (post) {
-                state[v] = 2;
-                continue;
-            }
-            if (state[v] == 1) return set_error(RT_ERR_ARG, "BVH contains a cycle");
-            if (state[v] == 2) continue;
-            state[v] = 1;
-            st.push_back({v, true});
-            const rt_bvh_node& nd = nodes[v];
-            if (nd.object_idx != 0xFFFFFFFFu) continue;
-            for (const uint32_t c : {nd.left_idx, nd.right_idx}) {
-                if (c == kRecNoRef) continue;
-                if (c >= NN) return set_error(RT_ERR_ARG, "BVH child index out of range");
-                st.push_back({c, false});
-            }
-        }
-    }
-    std::vector<uint32_t> cid(NN, kRecNoRef);
-    size_t n_int = 0, n_leaf = 0;
-    for (size_t n = 0; n < NN; ++n) {
-        if (nodes[n].object_idx == 0xFFFFFFFFu) cid[n] = uint32_t(n_int++);
-        else if (nodes[n].object_idx < P) cid[n] = kRecLeafBit | uint32_t(n_leaf++);
-    }
-    if (nodes[0].object_idx != 0xFFFFFFFFu) {  // a leaf root: no records (rt_scene_create makes none)
-        info[0] = 2;
-        info[1] = 0;
-        info[2] = 0;
-        return RT_OK;
-    }
-    const rt::FrustumRecords fr = rt::build_frustum_records(nodes, NN, cid.data(), aabbs, std::clamp(max_log2, 2, 5), stack_cap);
-    info[0] = fr.log2;
-    info[1] = fr.bound;
-    info[2] = (int64_t)fr.nrec;
-    if (rec && rec_cap >= fr.rec.size() && !fr.rec.empty()) std::memcpy(rec, fr.rec.data(), fr.rec.size() * sizeof(float));
-    return RT_OK;
-}

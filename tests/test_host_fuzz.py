@@ -136,20 +136,37 @@ def test_bvh_builder_refuses_bad_indices():
 
 def test_frustum_record_builder_refuses_malformed_trees():
     """rt_debug_frustum_records takes caller BVH arrays (as rt_scene_create does): child indices
-    past the array, cycles and shared children are refused, not followed."""
+    past the array, cycles and shared children are refused, not followed.  rt_debug_scene_pack
+    (the host half of rt_scene_create) refuses the same trees, with the code and the message
+    rt_scene_create itself gives: its packing errors come before any device call."""
+    L = _lib.lib()
     hs = rt.HostScene.load_objs([REPO / "assets" / "meshes" / "sphere.obj"])
     nodes = np.array(hs.nodes, np.uint32)
     aabbs = np.array(hs.aabbs, np.float32)
+    tris = np.array(hs.triangles, np.float32)
     P = hs.num_triangles
     rng = np.random.default_rng(5)
     internal = np.nonzero(nodes[:, 3] == 0xFFFFFFFF)[0]
     info = (C.c_int64 * 3)()
+    pinfo, digests = (C.c_int64 * 21)(), (C.c_uint64 * 22)()
     refused = 0
+    messages = set()
     for k in range(60):
         bad = nodes.copy()
         n = int(rng.choice(internal))
         col = 1 + k % 2
         bad[n, col] = [len(nodes), len(nodes) + 7, 0, n, 0xFFFFFFFE, int(rng.choice(internal))][k % 6]
-        rc = _lib.lib().rt_debug_frustum_records(P, bad.ctypes.data, aabbs.ctypes.data, 5, 128, info, None, 0)
+        rc = L.rt_debug_frustum_records(P, bad.ctypes.data, aabbs.ctypes.data, 5, 128, info, None, 0)
         refused += rc != 0
+        rc_pack = L.rt_debug_scene_pack(P, bad.ctypes.data, aabbs.ctypes.data, tris.ctypes.data, pinfo, digests)
+        msg_pack = L.rt_last_error() if rc_pack else b""
+        assert rc_pack == rc
+        if rc_pack == 0:
+            continue  # (a tree that packs would go on to the device)
+        h = C.c_void_p()
+        rc_create = L.rt_scene_create(0, P, bad.ctypes.data, aabbs.ctypes.data, tris.ctypes.data, None, None, 0, None, 0,
+                                      C.byref(h))
+        assert rc_create == rc_pack == -1 and L.rt_last_error() == msg_pack and not h.value  # RT_ERR_ARG
+        messages.add(msg_pack)
     assert refused > 0
+    assert messages == {b"BVH child index out of range", b"BVH contains a cycle"}
