@@ -411,22 +411,24 @@ __global__ __launch_bounds__(BLOCK) void tile_cull_pair_kernel(PairParams PP) {
     cull_tiles(P, bx * BLOCK + (int)threadIdx.x);
 }
 
-// tile_cut_kernel over both frames: every wave takes its (list, group) units of frame A, then
-// of frame B.
+// tile_cut_kernel over both frames: the even waves take frame A's (list, group) units, the odd
+// waves frame B's, so a wave of this grid has about one unit (a wave that took its units of A
+// and then of B made the chain two units long).
 __global__ __launch_bounds__(BLOCK) void tile_cut_pair_kernel(PairParams PP) {
+    __shared__ CutScratch scratch[BLOCK / 64];
     __builtin_amdgcn_s_setprio(3);
     const uint32_t lane = lane_id();
-    const int waves = (int)(gridDim.x * (BLOCK / 64));
-    for (int f = 0; f < 2; ++f) {
-        const RenderParams& P = f ? PP.f[1] : PP.f[0];
-        float box[6] = {0.f, 0.f, 0.f, -1.f, -1.f, -1.f};
-        int max_len;
-        const bool test = cut_setup(P, lane, box, max_len);
-        for (int p = (int)(blockIdx.x * (BLOCK / 64) + threadIdx.x / 64);; p += waves) {
-            const int q = p % P.nqueues, g = p / P.nqueues;
-            if (CUT_GROUP * g >= max_len) break;
-            (void)cut_unit(P, lane, q, g, test, box);
-        }
+    const int wib = (int)uni(threadIdx.x / 64);  // (wave-uniform, and known to be)
+    const int wave = (int)(blockIdx.x * (BLOCK / 64)) + wib;
+    const int waves = (int)(gridDim.x * (BLOCK / 64)) / 2;
+    const RenderParams& P = (wave & 1) ? PP.f[1] : PP.f[0];
+    float box[6] = {0.f, 0.f, 0.f, -1.f, -1.f, -1.f};
+    int max_len;
+    const bool test = cut_setup(P, lane, box, max_len);
+    for (int p = wave >> 1;; p += waves) {
+        const int q = p % P.nqueues, g = p / P.nqueues;
+        if (CUT_GROUP * g >= max_len) break;
+        (void)cut_unit(P, lane, q, g, test, box, scratch[wib]);
     }
 }
 
@@ -624,7 +626,7 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     DevBuf qent, qhdr;  // fnode quantised (build_quant_records): the big-scene kernels' records
     DevBuf fault;     // one word: RT_FAULT_* bits the kernels OR in (rt_scene_faults)
     DevBuf cut;  // tile culling: boxes of a cut of the tree (6 floats each)
-    DevBuf cut2;  // 2^cut_sub_log2 boxes below each cut box (tile_cut_sub), 6 floats each
+    DevBuf cut2;  // 2^cut_sub_log2 boxes below each cut box (cut_unit's second level), 6 floats each
     DevBuf tri;         // deep: triangles by index (brute-force completion)
     DevBuf work;  // kSets counter sets, then kSets x (live lists | cut survivor lists | heavy lists)
     int64_t last_tiles_total = 0;
@@ -1121,7 +1123,7 @@ int launch_prepasses(rt_scene* s, const RenderParams& P, int slot) {
     HIP_TRY(hipGetLastError());
     if (cut) {
         // 16 waves per CU; each takes (list, group) pairs grid-stride (c3: about one each)
-        const int cut_blocks = 4 * s->cus;
+        const int cut_blocks = 4 * s->cus * (8 / CUT_GROUP);
         hipExtLaunchKernelGGL(tile_cut_kernel, dim3(cut_blocks), dim3(BLOCK), 0, s->prep, nullptr, s->pdone[slot], 0, P);
         HIP_TRY(hipGetLastError());
     }
@@ -1450,7 +1452,7 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
             if (cut) {
                 // 32 waves per CU (the cut kernel's occupancy): the pair's cut mostly runs after
                 // the previous pair kernel has left the GPU, latency-bound per unit
-                hipExtLaunchKernelGGL(tile_cut_pair_kernel, dim3(8 * s->cus), dim3(BLOCK), 0, pp, nullptr,
+                hipExtLaunchKernelGGL(tile_cut_pair_kernel, dim3(8 * s->cus * (8 / CUT_GROUP)), dim3(BLOCK), 0, pp, nullptr,
                                       s->pdone[slot], 0, PP);
                 HIP_TRY(hipGetLastError());
             }

@@ -1,5 +1,5 @@
 // rt_prepass.hpp — the frame's pre-passes: tile bounds, the root-box cull (tile_cull_kernel),
-// the tree-cut cull with its second level (tile_cut_kernel, tile_cut_sub), the work lists and
+// the tree-cut cull with its second level (tile_cut_kernel, cut_unit), the work lists and
 // the heavy-first classes.  Exact: a tile is culled only when every ray of it provably misses
 // a box SearchBVH must pass before any triangle below it.  DESIGN.md §4.1, §4.4, §4.16.
 // Part of rt_device.hip's translation unit, included inside its anonymous namespace after rt_shade.hpp.
@@ -308,18 +308,47 @@ __global__ __launch_bounds__(BLOCK) void tile_cull_kernel(RenderParams P) {
     cull_tiles(P, (int)(blockIdx.x * BLOCK + threadIdx.x));
 }
 
-// Pass 2 (sc.ncut > 0), one wave per CUT_GROUP consecutive slots of a live list, one lane
-// per box of the cut (sc.cut, <= 64 boxes that hold every leaf exactly once): a tile is culled
-// when every lane proves its box missed by every ray of the tile (tile_misses_box_f; the tile
-// bounds are wave-uniform).  A culled tile gets its miss pixels here; the others go to list q's
+// Pass 2 (sc.ncut > 0), one wave per CUT_GROUP consecutive slots of a live list: a tile is
+// culled when every box of the cut (sc.cut, <= 64 boxes that hold every leaf exactly once) is
+// provably missed by every ray of the tile (tile_misses_box_f), or every sub-box (sc.cut2) of
+// the boxes that are not.  A culled tile gets its miss pixels here; the others go to list q's
 // heavy lists (below) or its survivor list, one atomic per (wave, list): the render kernel's
 // blocks then find only real tiles (a block for a culled or moved slot that leaves at once still
-// cost its launch and loads).  The pass runs on the scene's prep stream, overlapping the
-// previous frame's render kernel, so its atomics are off the critical path.
+// cost its launch and loads).  The pass runs on the scene's prep stream in the previous frame's
+// render kernel's tail, and the next render kernel waits for its end, so a unit is laid out as
+// few dependent steps (cut_unit), not as a loop over its tiles.
 #ifndef RT_CUT_GROUP
 #define RT_CUT_GROUP 8
 #endif
-constexpr int CUT_GROUP = RT_CUT_GROUP;
+constexpr int CUT_GROUP = RT_CUT_GROUP;  // 8, 4 or 2 (a power of two <= 8)
+static_assert(CUT_GROUP == 8 || CUT_GROUP == 4 || CUT_GROUP == 2, "RT_CUT_GROUP: 8, 4 or 2");
+// A wave's LDS for one unit: its tiles' bounds (written by the lane that owns the tile, read by
+// every lane).
+constexpr int CUT_T_FLOATS = 16;  // c, Dl, Dh, iDl, iDh (3 each), scale
+struct alignas(16) CutScratch {  // (rows of four float4)
+    float T[CUT_GROUP][CUT_T_FLOATS];
+};
+// Orders a wave's own LDS stores before its later LDS loads of other lanes' words (the LDS
+// executes one wave's instructions in order; this keeps the compiler from moving them).
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ TileDirsF cut_load_dirs(const float* t) {
+    TileDirsF T;
+    const float4 a = *reinterpret_cast<const float4*>(t), b = *reinterpret_cast<const float4*>(t + 4),
+                 c = *reinterpret_cast<const float4*>(t + 8), d = *reinterpret_cast<const float4*>(t + 12);
+    T.c[0] = a.x, T.c[1] = a.y, T.c[2] = a.z;
+    T.Dl[0] = a.w, T.Dl[1] = b.x, T.Dl[2] = b.y;
+    T.Dh[0] = b.z, T.Dh[1] = b.w, T.Dh[2] = c.x;
+    T.iDl[0] = c.y, T.iDl[1] = c.z, T.iDl[2] = c.w;
+    T.iDh[0] = d.x, T.iDh[1] = d.y, T.iDh[2] = d.z;
+    T.scale = d.w;
+    T.usable = T.scale > 0.0f && T.scale < 1e30f;  // (tile_dirs_f's own condition)
+    return T;
+}
+
 // The cut pass's test condition and this lane's box of the cut (loaded once per wave).
 __device__ __forceinline__ bool cut_setup(const RenderParams& P, uint32_t lane, float* box, int& max_len) {
     int n = 0;
@@ -340,40 +369,48 @@ __device__ __forceinline__ bool cut_setup(const RenderParams& P, uint32_t lane, 
     return test;
 }
 
-// The cut's second level for one tile: hm = the cut boxes some ray of the tile may reach (a
-// wave-uniform mask).  Their sub-boxes (sc.cut2: S = 2^cut_sub_log2 per cut box, a cut of its
-// subtree) are tested 64 at a time, 64 / S cut boxes per pass, lane l taking sub-box l % S of
-// the (l / S)-th remaining box of hm.  True when a sub-box may be reached; false when every one
-// is provably missed by every ray of the tile, which, with the cut boxes outside hm, proves that
-// no ray reaches any leaf (each leaf has an ancestor-or-self among the tested boxes, and
-// SearchBVH reaches a triangle only after every ancestor's box test passed).
-__device__ __forceinline__ bool tile_cut_sub(const RenderParams& P, const TileDirsF& T, uint64_t hm, uint32_t lane) {
-    const int sl = P.sc.cut_sub_log2;
-    const int per = 64 >> sl;
-    const int gi = (int)(lane >> sl);
-    const uint32_t c = lane & ((1u << sl) - 1u);
-    while (hm != 0) {
-        int mine = -1;
-        for (int k = 0; k < per && hm != 0; ++k) {
-            const int b = __builtin_ctzll(hm);
-            if (gi == k) mine = b;
-            hm &= hm - 1;
-        }
-        bool reach = false;
-        if (mine >= 0) {
-            const float* p = P.sc.cut2 + 6 * (((size_t)mine << sl) | c);
-            const float bx[6] = {p[0], p[1], p[2], p[3], p[4], p[5]};
-            reach = !tile_misses_box_f(T, bx);
-        }
-        if (ballot(reach) != 0) return true;
+// The second level hands out places: a pass has `per` = 64 >> cut_sub_log2 of them (lane l:
+// place l >> cut_sub_log2, sub-box l % S of the place's cut box).  This gives slot j's next cut
+// boxes (h: those not yet handed out) the places from `used` on and returns this lane's pair
+// (slot << 6 | cut box; `mine` when the lane's place is not among them).  Wave-uniform but for
+// the lane's own place.
+__device__ __forceinline__ int cut_sub_take(uint64_t& h, int j, int per, int place, int& used, int mine) {
+    while (h != 0 && used < per) {
+        const int b = __builtin_ctzll(h);
+        h &= h - 1;
+        if (place == used) mine = j << 6 | b;
+        ++used;
     }
-    return false;
+    return mine;
+}
+
+// This lane's sub-box of the pair `mine` of cut_sub_take (sc.cut2: S = 2^cut_sub_log2 boxes
+// per cut box, a cut of its subtree).
+__device__ __forceinline__ void cut_sub_fetch(const RenderParams& P, int mine, uint32_t lane, float* bx) {
+    if (mine < 0) return;
+    const int sl = P.sc.cut_sub_log2;
+    const float* p = P.sc.cut2 + 6 * (((size_t)(mine & 63) << sl) | (lane & ((1u << sl) - 1u)));
+#pragma unroll
+    for (int i = 0; i < 6; ++i) bx[i] = p[i];
 }
 
 // One unit of the cut pass: group g (CUT_GROUP consecutive slots) of live list q; false when
-// the group is past the list's end.
+// the group is past the list's end.  S: this wave's LDS.
+//   1. lane j computes the bounds of the tile in slot j (tile_dirs_f once per tile, not once
+//      per lane) and leaves them in LDS;
+//   2. first level, lane = box of the cut: every slot's test before any branch on one (the
+//      tests are independent), hm[j] = the boxes some ray of tile j may reach;
+//   3. second level, over the whole group, 64 >> cut_sub_log2 (tile, reached box) pairs per
+//      pass: first every tile's first pass, all loaded before any is tested, then what is
+//      left, packed over the tiles; a tile leaves the work once a sub-box of it may be
+//      reached.  A tile no sub-box of which can be reached is culled: with the cut boxes outside
+//      hm[j] missed, each leaf has an ancestor-or-self among the missed boxes, and SearchBVH
+//      reaches a triangle only after every ancestor's box test passed;
+//   4. the miss pixels of all the group's culled tiles, the lanes split over the tiles;
+//   5. the appends.
+// The decisions are those of a loop over the tiles: the same boxes, the same test.
 __device__ __forceinline__ bool cut_unit(const RenderParams& P, uint32_t lane, int q, int g, bool test,
-                                         const float* box) {
+                                         const float* box, CutScratch& S) {
     const int len = (int)ldc_u32(&P.live_count[q * COUNTER_STRIDE]);
     if (CUT_GROUP * g >= len) return false;
     const int m = min(CUT_GROUP, len - CUT_GROUP * g);
@@ -382,24 +419,99 @@ __device__ __forceinline__ bool cut_unit(const RenderParams& P, uint32_t lane, i
     // the tile's last render cost, loaded before the tests so the load overlaps them
     uint2 cost = make_uint2(0u, 0u);
     if (P.heavy_cap > 0 && (int)lane < m) cost = *reinterpret_cast<const uint2*>(P.tile_cost + 4 * (size_t)my_tile);
-    uint64_t culled = 0;
-    for (int j = 0; test && j < m; ++j) {
-        const int tile = (int)rdlane((uint32_t)my_tile, (uint32_t)j);
-        const int tx = tile % P.tiles_x, ty = tile / P.tiles_x;
-        const int xa = tx * P.tile_w, ra = ty * P.tile_h;
-        const int xb = min(xa + P.tile_w, P.W) - 1, rb = min(ra + P.tile_h, P.rows) - 1;
-        const TileDirsF T = tile_dirs_f(P, xa, xb, global_row(P, ra), global_row(P, rb));
-        const bool hit = (int)lane < P.sc.ncut && !tile_misses_box_f(T, box);
+    uint32_t culled = 0;  // a mask of slots
+    if (test) {
+        wave_lds_sync();  // (the previous unit's loads of S are done)
+        if ((int)lane < m) {
+            const int tx = my_tile % P.tiles_x, ty = my_tile / P.tiles_x;
+            const int xa = tx * P.tile_w, ra = ty * P.tile_h;
+            const int xb = min(xa + P.tile_w, P.W) - 1, rb = min(ra + P.tile_h, P.rows) - 1;
+            const TileDirsF T = tile_dirs_f(P, xa, xb, global_row(P, ra), global_row(P, rb));
+            float4* t = reinterpret_cast<float4*>(S.T[lane]);
+            t[0] = make_float4(T.c[0], T.c[1], T.c[2], T.Dl[0]);
+            t[1] = make_float4(T.Dl[1], T.Dl[2], T.Dh[0], T.Dh[1]);
+            t[2] = make_float4(T.Dh[2], T.iDl[0], T.iDl[1], T.iDl[2]);
+            t[3] = make_float4(T.iDh[0], T.iDh[1], T.iDh[2], T.scale);
+        }
+        wave_lds_sync();
+        uint64_t hm[CUT_GROUP];
+#pragma unroll
+        for (int j = 0; j < CUT_GROUP; ++j) {
+            bool hit = false;
+            if (j < m && (int)lane < P.sc.ncut) hit = !tile_misses_box_f(cut_load_dirs(S.T[j]), box);
+            hm[j] = ballot(hit);
+        }
 #ifdef RT_WAVE_TIMES
-        {
-            const uint64_t hm = ballot(hit);
-            if (g_cut_counts && lane == 0) g_cut_counts[tile] = __popcll(hm);
+        if (g_cut_counts) {
+#pragma unroll
+            for (int j = 0; j < CUT_GROUP; ++j)
+                if ((int)lane == j && j < m) g_cut_counts[my_tile] = __popcll(hm[j]);
         }
 #endif
-        const uint64_t hm = ballot(hit);
-        if (hm == 0 || (P.sc.cut_sub_log2 > 0 && !tile_cut_sub(P, T, hm, lane))) {
-            write_culled_tile(P, tile, (int)lane, 64);
-            culled |= 1ull << j;
+        uint32_t open = 0;  // slots whose tile may reach a cut box
+#pragma unroll
+        for (int j = 0; j < CUT_GROUP; ++j)
+            if (hm[j] != 0) open |= 1u << j;
+        uint32_t reached = open;
+        if (P.sc.cut_sub_log2 > 0 && open != 0) {
+            const int per = 64 >> P.sc.cut_sub_log2, place = (int)(lane >> P.sc.cut_sub_log2);
+            reached = 0;
+            // every tile's first pass (its first `per` boxes) at once: the passes do not depend
+            // on each other, so all their sub-boxes are loaded before the first test
+            int first[CUT_GROUP];
+            float fbx[CUT_GROUP][6];
+#pragma unroll
+            for (int j = 0; j < CUT_GROUP; ++j) {
+                int used = 0;
+                first[j] = cut_sub_take(hm[j], j, per, place, used, -1);
+                cut_sub_fetch(P, first[j], lane, fbx[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < CUT_GROUP; ++j) {
+                if (!((open >> j) & 1u)) continue;
+                bool reach = false;
+                if (first[j] >= 0) reach = !tile_misses_box_f(cut_load_dirs(S.T[j]), fbx[j]);
+                if (ballot(reach) != 0) reached |= 1u << j;
+            }
+            // the tiles with more boxes than a pass holds and none of the first reached (few):
+            // their remaining boxes, packed over the tiles, until each is reached or out of boxes
+            for (;;) {
+                uint32_t pend = 0;
+#pragma unroll
+                for (int j = 0; j < CUT_GROUP; ++j)
+                    if (hm[j] != 0) pend |= 1u << j;
+                pend &= ~reached;
+                if (pend == 0) break;
+                int used = 0, mine = -1;
+#pragma unroll
+                for (int j = 0; j < CUT_GROUP; ++j)
+                    if ((pend >> j) & 1u) mine = cut_sub_take(hm[j], j, per, place, used, mine);
+                float bx[6];
+                cut_sub_fetch(P, mine, lane, bx);
+                bool reach = false;
+                if (mine >= 0) reach = !tile_misses_box_f(cut_load_dirs(S.T[mine >> 6]), bx);
+#pragma unroll
+                for (int t = 0; t < CUT_GROUP; ++t)
+                    if (ballot(reach && (mine >> 6) == t) != 0) reached |= 1u << t;
+            }
+        }
+        culled = ((1u << m) - 1u) & ~reached;
+        if (culled != 0) {
+            // the culled tiles' miss pixels: 64 / (their count, rounded up to a power of two)
+            // lanes per tile
+            const int nc = __popc(culled);
+            const int sh = nc > 4 ? 3 : nc > 2 ? 2 : nc > 1 ? 1 : 0;
+            const int k = (int)(lane >> (6 - sh));  // this lane writes the k-th culled tile
+            int slot = -1, seen = 0;
+#pragma unroll
+            for (int t = 0; t < CUT_GROUP; ++t) {
+                if ((culled >> t) & 1u) {
+                    if (seen == k) slot = t;
+                    ++seen;
+                }
+            }
+            const int tile = __builtin_amdgcn_ds_bpermute(4 * max(slot, 0), my_tile);
+            if (slot >= 0) write_culled_tile(P, tile, (int)(lane & ((64u >> sh) - 1u)), 64 >> sh);
         }
     }
     // Heavy-first: a surviving tile whose last render took >= heavy_ticks[c] goes to list q's
@@ -407,7 +519,7 @@ __device__ __forceinline__ bool cut_unit(const RenderParams& P, uint32_t lane, i
     // The appends take one vector atomic, lane k adding class k's count (lane NCLASS the
     // survivors'), so a group pays one round trip for them.
     int cls = -1;  // -1: no tile, or culled
-    if ((int)lane < m && !((culled >> lane) & 1ull)) {
+    if ((int)lane < m && !((culled >> lane) & 1u)) {
         cls = NCLASS;
         if (P.heavy_cap > 0) {
             const uint32_t mx = max(max(cost.x & 0xffffu, cost.x >> 16), max(cost.y & 0xffffu, cost.y >> 16));
@@ -449,17 +561,19 @@ __device__ __forceinline__ bool cut_unit(const RenderParams& P, uint32_t lane, i
 }
 
 __global__ __launch_bounds__(BLOCK) void tile_cut_kernel(RenderParams P) {
+    __shared__ CutScratch scratch[BLOCK / 64];
     __builtin_amdgcn_s_setprio(3);
     const uint32_t lane = lane_id();
     const int waves = (int)(gridDim.x * (BLOCK / 64));
+    const int wib = (int)uni(threadIdx.x / 64);  // (wave-uniform, and known to be)
     float box[6] = {0.f, 0.f, 0.f, -1.f, -1.f, -1.f};
     int max_len;
     const bool test = cut_setup(P, lane, box, max_len);
     // (list q, group g) pairs, lists interleaved, each wave from its own index on
-    for (int p = (int)(blockIdx.x * (BLOCK / 64) + threadIdx.x / 64);; p += waves) {
+    for (int p = (int)(blockIdx.x * (BLOCK / 64)) + wib;; p += waves) {
         const int q = p % P.nqueues, g = p / P.nqueues;
         if (CUT_GROUP * g >= max_len) break;
-        (void)cut_unit(P, lane, q, g, test, box);
+        (void)cut_unit(P, lane, q, g, test, box, scratch[wib]);
     }
 #ifdef RT_FRAME_SPAN
     if (lane == 0 && g_frame_span) atomicMax(&g_frame_span[4 * (P.drain_tag & 255u) + 3], wall_clock64());

@@ -239,7 +239,7 @@ void pack_bounds(const Tree& t, PackedScene& out) {
 // ancestor-or-self in the set; a missing child (NO_REF) holds no leaf.
 // Second level (RT_TUNE_CUT_SUB sub-boxes per cut box, a power of two <= 64): the same rule
 // inside each cut node's subtree, so the tiles whose rays reach a cut box are tested against the
-// boxes below it (tile_cut_sub).  Unused slots repeat the node's first sub-box: a duplicate
+// boxes below it (cut_unit).  Unused slots repeat the node's first sub-box: a duplicate
 // changes no "every box missed" decision.
 void pack_cut(const Tree& t, PackedScene& out) {
     if (t.cid[0] == NO_REF || (t.cid[0] & LEAF_BIT)) return;
