@@ -509,6 +509,20 @@ int rt_powf_batch(int device, const float* x, const float* y, int n, float* out)
 int rt_box_test_host(const float* rays, const float* boxes, const float* tminmax, int n,
                      int32_t* out_fast, int32_t* out_exact, int32_t* out_class);
 
+/* The device build of the same tests (v_rcp_f32 reciprocals, packed FMAs, the wave forms with
+ * their ballots), item i in lane i % 64 of a 256-thread block over 256 consecutive items, the
+ * ray prepared by make_ray as the render kernels prepare it.  bmax: NULL for the per-item bounds
+ * rt_box_test_host derives (inf for an inverted or NaN box), else n*3 floats, the caller's
+ * per-axis bounds of |coordinate| (at least the box's own; larger ones model a scene's).
+ * active: NULL for all items, else n bytes; the wave forms run for the lanes with a nonzero byte
+ * and i < n (every lane of a wave calls them).  out: n*5 ints per item: [0] box_hit, [1]
+ * box_classify (0 miss / 1 hit / 2 ambiguous), [2] [3] [4] the lane's bit of box_hit_mask<PK, XL>
+ * for (PK, XL) = (0, 0), (1, 0), (1, 1), the forms the traversals instantiate, 0 for a lane
+ * outside `active`.  [0] and [1] take tmin from tminmax; the wave forms' tmin is the traversals'
+ * constant 1e-4f. */
+int rt_box_test_batch(int device, const float* rays, const float* boxes, const float* tminmax,
+                      const float* bmax, const uint8_t* active, int n, int32_t* out);
+
 /* Host build of the camera rays' frustum records rt_scene_create makes (no device): for a BVH
  * of P triangles (the same arrays as rt_scene_create), the records of arity 2^info[0]
  * (8 x 2^info[0] floats each: per entry the (min, max) pairs of x, y, z, then the entries'

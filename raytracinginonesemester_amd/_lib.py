@@ -192,6 +192,7 @@ SIGNATURES = {
     "rt_debug_scene_pack": (I, [SZ, P, P, P, P, P]),
     "rt_powf_batch": (I, [I, P, P, I, P]),
     "rt_box_test_host": (I, [P, P, P, I, P, P, P]),
+    "rt_box_test_batch": (I, [I, P, P, P, P, P, I, P]),
     "rt_kernel_times": (I, [P, P, I, P]),
     "rt_frame_times": (I, [P, P, I, P]),
     "rt_prepass_times": (I, [P, P, I, P]),

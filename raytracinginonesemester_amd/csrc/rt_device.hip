@@ -93,7 +93,6 @@ constexpr int MODE_QR = 256;
 constexpr int REF_STACK = 512;                // query.h:245
 constexpr uint32_t INV_LEAF = 0xFFFFFFFEu;    // deep stack entry: a leaf naming no triangle (query.h:263)
 constexpr uint32_t BRUTE_BIT = 0x40000000u;   // HitState::slot of a brute-force hit: BRUTE_BIT | triangle
-constexpr float kRayTMin = 1e-4f;             // query.h:233
 constexpr float RT_EPS = 1e-3f;               // shader.h:22
 
 struct DevMaterial {  // rt_material, read through a 4-byte aligned pointer
@@ -582,6 +581,46 @@ __global__ __launch_bounds__(BLOCK) void powf_kernel(const float* __restrict__ x
                                                      float* __restrict__ out) {
     const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
     if (i < n) out[i] = ref_powf(x[i], y[i]);
+}
+
+// rt_box_test_batch: the device build of the box tests, item i in lane i & 63 of its wave.  Every
+// lane of a wave runs every form (the mask forms ballot); lanes past n repeat item n - 1 outside
+// `act` and store nothing.
+__global__ __launch_bounds__(BLOCK) void box_test_kernel(const float* __restrict__ rays, const float* __restrict__ boxes,
+                                                         const float* __restrict__ tminmax,
+                                                         const float* __restrict__ bmax,
+                                                         const uint8_t* __restrict__ active, int n,
+                                                         int32_t* __restrict__ out) {
+    const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    const bool in = i < n;
+    const size_t j = (size_t)(in ? i : n - 1);  // n > 0 (the host returns before the launch otherwise)
+    const float* R = rays + 6 * j;
+    const float* B = boxes + 6 * j;
+    f3 bm;
+    if (bmax != nullptr) {
+        bm = mk(bmax[3 * j], bmax[3 * j + 1], bmax[3 * j + 2]);
+    } else {  // as rt_box_test_host
+        bm = mk(fmaxf(fabsf(B[0]), fabsf(B[3])), fmaxf(fabsf(B[1]), fabsf(B[4])), fmaxf(fabsf(B[2]), fabsf(B[5])));
+        if (!(B[0] <= B[3] && B[1] <= B[4] && B[2] <= B[5])) bm = mk(INFINITY, INFINITY, INFINITY);
+    }
+    const BoxP b = {(v2f){B[0], B[3]}, (v2f){B[1], B[4]}, (v2f){B[2], B[5]}};
+    const float tmin = tminmax[2 * j], tmax = tminmax[2 * j + 1];
+    const RayPre r = make_ray(mk(R[0], R[1], R[2]), mk(R[3], R[4], R[5]), bm, tmin);
+    const RayPre rw = make_ray(r.o, r.d, bm);  // the wave forms' tmin is the traversals'
+    const uint64_t act = ballot(in && (active == nullptr || active[j] != 0));
+    const int cls = box_classify(r, b, tmax);
+    const bool h = box_hit(r, b, tmin, tmax);
+    const uint64_t m0 = box_hit_mask<false, false>(rw, b, tmax, act);
+    const uint64_t m1 = box_hit_mask<true, false>(rw, b, tmax, act);
+    const uint64_t m2 = box_hit_mask<true, true>(rw, b, tmax, act);
+    if (in) {
+        int32_t* O = out + 5 * j;
+        O[0] = h ? 1 : 0;
+        O[1] = cls;
+        O[2] = lane_in(m0) ? 1 : 0;
+        O[3] = lane_in(m1) ? 1 : 0;
+        O[4] = lane_in(m2) ? 1 : 0;
+    }
 }
 
 // Batched ray-triangle queries (KAT path): one lane per ray.
@@ -1920,6 +1959,31 @@ extern "C" int rt_powf_batch(int device, const float* x, const float* y, int n, 
     return RT_OK;
 }
 
+extern "C" int rt_box_test_batch(int device, const float* rays, const float* boxes, const float* tminmax,
+                                 const float* bmax, const uint8_t* active, int n, int32_t* out) {
+    if (n < 0 || (n > 0 && (!rays || !boxes || !tminmax || !out)))
+        return set_error(RT_ERR_ARG, "rt_box_test_batch: bad args");
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(device);
+    DevBuf dr, db, dt, dm, da, dout;
+    if ((rc = dr.upload(rays, size_t(n) * 6 * sizeof(float))) != RT_OK) return rc;
+    if ((rc = db.upload(boxes, size_t(n) * 6 * sizeof(float))) != RT_OK) return rc;
+    if ((rc = dt.upload(tminmax, size_t(n) * 2 * sizeof(float))) != RT_OK) return rc;
+    if (bmax && (rc = dm.upload(bmax, size_t(n) * 3 * sizeof(float))) != RT_OK) return rc;
+    if (active && (rc = da.upload(active, size_t(n))) != RT_OK) return rc;
+    if ((rc = dout.alloc(size_t(n) * 5 * sizeof(int32_t))) != RT_OK) return rc;
+    hipLaunchKernelGGL(box_test_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr,
+                       static_cast<const float*>(dr.p), static_cast<const float*>(db.p), static_cast<const float*>(dt.p),
+                       bmax ? static_cast<const float*>(dm.p) : nullptr,
+                       active ? static_cast<const uint8_t*>(da.p) : nullptr, n, static_cast<int32_t*>(dout.p));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, size_t(n) * 5 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 extern "C" int rt_box_test_host(const float* rays, const float* boxes, const float* tminmax, int n,
                                 int32_t* out_fast, int32_t* out_exact, int32_t* out_class) {
     if (n < 0 || (n > 0 && (!rays || !boxes || !tminmax || !out_fast || !out_exact || !out_class)))
@@ -1929,9 +1993,9 @@ extern "C" int rt_box_test_host(const float* rays, const float* boxes, const flo
         const float* B = boxes + 6 * i;
         f3 bm = mk(fmaxf(fabsf(B[0]), fabsf(B[3])), fmaxf(fabsf(B[1]), fabsf(B[4])), fmaxf(fabsf(B[2]), fabsf(B[5])));
         if (!(B[0] <= B[3] && B[1] <= B[4] && B[2] <= B[5])) bm = mk(INFINITY, INFINITY, INFINITY);  // as rt_scene_create
-        const RayPre r = make_ray(mk(R[0], R[1], R[2]), mk(R[3], R[4], R[5]), bm);
+        const RayPre r = make_ray(mk(R[0], R[1], R[2]), mk(R[3], R[4], R[5]), bm, tminmax[2 * i]);
         const BoxP b = {(v2f){B[0], B[3]}, (v2f){B[1], B[4]}, (v2f){B[2], B[5]}};
-        out_class[i] = box_classify(r, b, tminmax[2 * i], tminmax[2 * i + 1]);
+        out_class[i] = box_classify(r, b, tminmax[2 * i + 1]);
         out_fast[i] = box_hit(r, b, tminmax[2 * i], tminmax[2 * i + 1]) ? 1 : 0;
         out_exact[i] = box_hit_exact(r, b, (double)tminmax[2 * i], (double)tminmax[2 * i + 1]) ? 1 : 0;
     }

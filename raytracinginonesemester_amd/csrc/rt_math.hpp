@@ -49,6 +49,7 @@ struct BoxP {
 
 // Relative slack of the float pre-classification (see box_classify).
 constexpr float kBoxRel = 1e-6f;
+constexpr float kRayTMin = 1e-4f;  // query.h:233: the tmin of every traversal's box and triangle tests
 
 // A ray as the slab test needs it.  `par` bit a: |dir[a]| < 1e-8f, where intersectAABB
 // degenerates to an exact inside test on that axis (bvh.h:90-91).  iv is a float reciprocal
@@ -56,7 +57,7 @@ constexpr float kBoxRel = 1e-6f;
 // ivp = max(iv, 0) and ivn = min(iv, 0); c1 = -o*iv - E, c2 = -o*iv + E and e2 = 2E with a
 // per-ray error bound E (box_classify).  A ray with a parallel axis, or whose slab parameters
 // could come near the float range ((bmax + |o|) |iv| >= 1e37 on some axis, or not finite),
-// gets c1 = c2 = NaN and hit_lim = -inf: every test of it is ambiguous (exact path).  They
+// gets c1 = c2 = NaN and tmin_pre = NaN: every test of it is ambiguous (exact path).  They
 // serve the pre-classification only, never the decision of an ambiguous case.
 struct RayPre {
     f3 o, d;
@@ -64,7 +65,7 @@ struct RayPre {
     v2f cx, cy, cz;     // per axis (c1, c2)
     f3 e2;
     float m2;       // 2 max(e2): the one-margin HIT test's (box_sure_hit1); +inf if unsafe
-    float hit_lim;  // +inf, or -inf for a ray the pre-classification does not handle
+    float tmin_pre;  // the box tests' tmin, or NaN for a ray the pre-classification does not handle
     uint32_t par;
 };
 
@@ -77,8 +78,9 @@ __host__ __device__ __forceinline__ float rcp_approx(float x) {
 }
 
 // bmax: per axis, an upper bound of |coordinate| over every box the ray will be tested
-// against (the scene's; make_ray_mt for rays that meet no box).
-__host__ __device__ __forceinline__ RayPre make_ray(f3 o, f3 d, f3 bmax) {
+// against (the scene's; make_ray_mt for rays that meet no box).  tmin: the tmin of every box
+// test the ray will take (the traversals' kRayTMin).
+__host__ __device__ __forceinline__ RayPre make_ray(f3 o, f3 d, f3 bmax, float tmin = kRayTMin) {
     RayPre r;
     r.o = o;
     r.d = d;
@@ -111,7 +113,7 @@ __host__ __device__ __forceinline__ RayPre make_ray(f3 o, f3 d, f3 bmax) {
     r.cz = (v2f){c1[2], c2[2]};
     r.e2 = mk(e2[0], e2[1], e2[2]);
     r.m2 = safe ? 2.0f * fmaxf(fmaxf(e2[0], e2[1]), e2[2]) : INFINITY;
-    r.hit_lim = safe ? INFINITY : -INFINITY;
+    r.tmin_pre = safe ? tmin : NAN;
     return r;
 }
 
@@ -191,11 +193,14 @@ __host__ __device__ inline bool box_hit_exact(const RayPre& r, const BoxP& b, do
 //   MISS  if max(tmin, lowLo) > min(tmax, highHi)     (then Lmax > Hmin: reference rejects)
 //   HIT   if max(tmin, lowHi) <= min(tmax, highLo)    (then Lmax <= Hmin: reference accepts)
 // For a safe ray (make_ray) every estimate is finite and below 1e37 in magnitude, far from
-// overflow.  An unsafe ray's estimates are NaN, which the max/min drop: MISS reads
-// tmin > tmax (true only when the reference rejects anyway), and HIT is ruled out by folding
-// hit_lim = -inf into its min.  The
-// reference's parallel-axis inside test is only taken by unsafe rays, so it never needs a
-// float counterpart.
+// overflow.  An unsafe ray's estimates are NaN and so is the tmin folded into Lc and into the
+// HIT tests (tmin_pre; max and min drop a NaN beside a number, but of two NaNs they return NaN):
+// Lc is NaN, every compare with it is false, and neither MISS nor HIT is read.  Every test of an
+// unsafe ray is decided in double.  (With a plain tmin there, MISS read tmin > tmax for an unsafe
+// ray, which the reference does not reject for a ray parallel to all three axes: its answer is
+// the inside test whatever tmin and tmax are.  No traversal makes that input, tmax being a bestT
+// >= tmin; tests/box_cases.py's degenerate set does.)  The reference's parallel-axis inside test
+// is only taken by unsafe rays, so it never needs a float counterpart.
 enum : int { BOX_MISS = 0, BOX_HIT = 1, BOX_AMBIG = 2 };
 // The per-axis padded ends lo' - E (lL) and hi' + E (hH).
 struct AxisEnds {
@@ -237,7 +242,7 @@ __device__ __forceinline__ AxisEnds box_ends_pk(const RayPre& r, const BoxP& b) 
 #else
 __device__ __forceinline__ AxisEnds box_ends_pk(const RayPre& r, const BoxP& b) { return box_ends(r, b); }  // host pass: parsed, never emitted
 #endif
-// Lc = max(tmin, lowLo) and Hc = min(tmax, highHi): MISS iff Lc > Hc.
+// Lc = max(tmin, lowLo) and Hc = min(tmax, highHi): MISS iff Lc > Hc.  tmin: the ray's tmin_pre.
 struct BoxEnds {
     float Lc, Hc;
 };
@@ -250,23 +255,25 @@ __host__ __device__ __forceinline__ bool box_miss(const BoxEnds& c) { return c.L
 // the slack of E).  Cheap; ambiguous cases go on to box_sure_hit2.
 __host__ __device__ __forceinline__ bool box_sure_hit1(const RayPre& r, const BoxEnds& c) { return c.Lc + r.m2 <= c.Hc; }
 // HIT with the per-axis margins.
-__host__ __device__ __forceinline__ bool box_sure_hit2(const RayPre& r, const AxisEnds& e, float tmin, float tmax) {
+__host__ __device__ __forceinline__ bool box_sure_hit2(const RayPre& r, const AxisEnds& e, float tmax) {
     const float lowHi = fmaxf(fmaxf(e.lLx + r.e2.x, e.lLy + r.e2.y), e.lLz + r.e2.z);
     const float highLo = fminf(fminf(e.hHx - r.e2.x, e.hHy - r.e2.y), e.hHz - r.e2.z);
-    return fmaxf(lowHi, tmin) <= fminf(fminf(highLo, tmax), r.hit_lim);
+    return fmaxf(lowHi, r.tmin_pre) <= fminf(highLo, tmax);
 }
 
-__host__ __device__ __forceinline__ int box_classify(const RayPre& r, const BoxP& b, float tmin, float tmax) {
+// (tmin is the one the ray was made with, make_ray.)
+__host__ __device__ __forceinline__ int box_classify(const RayPre& r, const BoxP& b, float tmax) {
     const AxisEnds e = box_ends(r, b);
-    const BoxEnds c = box_lc_hc(e, tmin, tmax);
+    const BoxEnds c = box_lc_hc(e, r.tmin_pre, tmax);
     if (box_miss(c)) return BOX_MISS;
-    if (box_sure_hit1(r, c) || box_sure_hit2(r, e, tmin, tmax)) return BOX_HIT;
+    if (box_sure_hit1(r, c) || box_sure_hit2(r, e, tmax)) return BOX_HIT;
     return BOX_AMBIG;
 }
 
-// intersectAABB with the float fast path; bit-identical answer to box_hit_exact.
+// intersectAABB with the float fast path; bit-identical answer to box_hit_exact.  tmin: the one
+// the ray was made with (make_ray).
 __host__ __device__ __forceinline__ bool box_hit(const RayPre& r, const BoxP& b, float tmin, float tmax) {
-    const int c = box_classify(r, b, tmin, tmax);
+    const int c = box_classify(r, b, tmax);
     if (c != BOX_AMBIG) return c == BOX_HIT;
     return box_hit_exact(r, b, (double)tmin, (double)tmax);
 }

@@ -57,11 +57,11 @@ __device__ __forceinline__ uint64_t box_hit_mask(const RayPre& r, const BoxP& b,
     AxisEnds e;
     if constexpr (PK) e = box_ends_pk(r, b);
     else e = box_ends(r, b);
-    const BoxEnds c = box_lc_hc(e, kRayTMin, tmax);
+    const BoxEnds c = box_lc_hc(e, r.tmin_pre, tmax);
     uint64_t hit = ballot(box_sure_hit1(r, c)) & act;
     uint64_t amb = act & ~(hit | ballot(box_miss(c)));
     if (amb == 0) return hit;
-    const uint64_t h2 = ballot(box_sure_hit2(r, e, kRayTMin, tmax)) & amb;
+    const uint64_t h2 = ballot(box_sure_hit2(r, e, tmax)) & amb;
     hit |= h2;
     amb &= ~h2;
     if (amb == 0) return hit;

@@ -129,3 +129,73 @@ def device_scene(name: str, device: int = 0):
 
     a = scene_arrays(name)
     return rt.DeviceScene(a["P"], a["nodes"], a["aabbs"], a["tris"], a["triobj"], a["mats"], a["lights"], device)
+
+
+# ---- the JSON scenes at other magnitudes ----------------------------------------------------
+# Every traversal's box decisions at coordinates the shipped scenes do not have: the arrays of a
+# base scene moved (vertices, triangles, lights and camera alike), the tree rebuilt by
+# rt.build_bvh over the moved vertices.
+#   scale_2^-10, scale_2^12  every coordinate times a power of two (exact);
+#   shift_x_4096             x + 4096 in float32: 12 low bits go, vertices coincide, boxes go flat;
+#   far_triangle             one more triangle with x near 2^100: the scene's bound on x passes
+#                            1e30, so the frustum family has no bound on x and make_ray's float
+#                            filter is off for every ray with a finite x slope.
+VARIANT_BASES = ("sphere_single", "cornell")
+VARIANTS = ("scale_2^-10", "scale_2^12", "shift_x_4096", "far_triangle")
+N_VARIANT_RAYS = 1024
+
+
+@lru_cache(maxsize=None)
+def variant_arrays(base: str, kind: str) -> dict:
+    """scene_arrays' keys for the moved scene, `camera(W, H)` (the base scene's camera moved the
+    same way) and its own 1024-ray batch with the oracle's answers (rays, idx, t)."""
+    import raytracinginonesemester_amd as rt
+    from conftest import host_scene
+
+    hs = host_scene(base + ".json")
+    f32 = np.float32
+    if kind.startswith("scale_"):
+        s = {"scale_2^-10": 2.0 ** -10, "scale_2^12": 2.0 ** 12}[kind]
+
+        def move(p):
+            return (np.asarray(p, f32) * f32(s)).astype(f32)
+    elif kind == "shift_x_4096":
+        def move(p):
+            return (np.asarray(p, f32) + np.array([4096.0, 0.0, 0.0], f32)).astype(f32)
+    else:
+        def move(p):
+            return np.asarray(p, f32).copy()
+    pos = move(hs.positions)
+    idx = hs.indices.copy()
+    tris = hs.triangles.copy()
+    tris[:, :9] = move(tris[:, :9].reshape(-1, 3)).reshape(-1, 9)
+    triobj = hs.tri_object_ids.copy()
+    lights = hs.lights.copy()
+    lights["position"] = move(lights["position"])
+    if kind == "far_triangle":
+        big = 2.0 ** 100
+        v = np.array([[big, 0.0, 0.0], [1.5 * big, 1.0, 0.0], [big, 0.0, 1.0]], f32)
+        idx = np.vstack([idx, np.arange(3, dtype=np.uint32)[None, :] + np.uint32(pos.shape[0])])
+        pos = np.vstack([pos, v])
+        tris = np.vstack([tris, np.concatenate([v.reshape(-1), np.tile(np.array([-1.0, 0.0, 0.0], f32), 3)])[None, :]])
+        triobj = np.concatenate([triobj, triobj[:1]])
+    nodes, aabbs = rt.build_bvh(pos, idx)
+    i = hs.info
+
+    def camera(W, H):
+        return rt.Camera(tuple(move(np.array(tuple(i.cam_position)))), tuple(move(np.array(tuple(i.cam_look_at)))),
+                         tuple(i.cam_up), i.focal_length_mm, i.sensor_height_mm, W, H)
+
+    a = {"P": int(idx.shape[0]), "nodes": nodes, "aabbs": aabbs, "tris": np.ascontiguousarray(tris, f32),
+         "triobj": np.ascontiguousarray(triobj), "mats": hs.materials, "lights": lights,
+         "light": np.array(lights[0]["position"], np.float64), "camera": camera}
+    # (far_triangle: around the base scene's root box; around its own, 2^100 wide, three classes
+    # in four would start near 1e30 and miss at the root)
+    around = hs.aabbs if kind == "far_triangle" else aabbs
+    rays = make_rays(around, a["tris"], a["light"], N_VARIANT_RAYS, SEED)
+    a["rays"] = rays
+    a["idx"], a["t"] = oracle_trace(a["P"], nodes, aabbs, a["tris"], rays)
+    for v in a.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return a

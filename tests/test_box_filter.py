@@ -7,7 +7,9 @@ huge coordinates, axis-parallel directions)."""
 from __future__ import annotations
 
 import numpy as np
+import pytest
 
+import box_cases as bc
 from raytracinginonesemester_amd import _lib
 
 
@@ -107,3 +109,44 @@ def test_near_parallel_and_overflow_scales():
         tmm = np.stack([np.full(n, 1e-4), rng.choice([3.4028235e38, 1.0, 1e30], size=n)], axis=1)
         fast, exact, _ = _run(np.concatenate([o, d], axis=1), boxes, tmm)
         assert np.array_equal(fast, exact), scale
+
+
+# ---- the sets of tests/box_cases.py, against a reference of their own ------------------------
+# (the tests above compare the pre-classified test with the project's own box_hit_exact; here
+# both must equal ref_aabb, numpy's restatement of bvh.h:81-129.  The scene-like-bounds sets of
+# tests/test_gpu_box_filter.py are these same items: the host entry point takes no bmax.)
+@pytest.mark.parametrize("name", bc.BOX_CASES)
+def test_sets_match_the_numpy_reference(name):
+    c = bc.box_case(name)
+    fast, exact, cls = _run(c["rays"], c["boxes"], c["tmm"])
+    ref = c["ref"].astype(np.int32)
+    bad = np.flatnonzero(exact != ref)
+    assert bad.size == 0, f"box_hit_exact: {bad.size} of {ref.size} differ from ref_aabb\n" + bc.hex_triples(c, bad)
+    bad = np.flatnonzero(fast != ref)
+    assert bad.size == 0, f"box_hit: {bad.size} of {ref.size} differ from ref_aabb\n" + bc.hex_triples(c, bad)
+    sure = cls != 2
+    bad = np.flatnonzero(sure & (cls != ref))
+    assert bad.size == 0, f"{bad.size} sure classes against ref_aabb\n" + bc.hex_triples(c, bad)
+    share = {k: float((cls == v).mean()) for k, v in (("miss", 0), ("hit", 1), ("ambiguous", 2))}
+    print(f"{name}: n {ref.size}, hit share {ref.mean():.3f}, host classes {share}")
+    if name in bc.RANDOM_CASES:  # the host reciprocal is exact: no ambiguous item without a parallel axis
+        assert (cls[bc.no_parallel_axis(c)] == 2).sum() == 0
+    if name == "bands":
+        assert all(v > 0 for v in share.values()), share
+    if name.startswith("aimed"):
+        assert 0.2 < ref.mean() < 0.8 and share["ambiguous"] > 0.2, (ref.mean(), share)
+
+
+def test_box_test_batch_refuses_bad_arguments():
+    """Null or negative arguments are RT_ERR_ARG before any device is looked for."""
+    L = _lib.lib()
+    RT_ERR_ARG = -1
+    f = np.zeros(6, np.float32)
+    out = np.zeros(5, np.int32)
+    p, po = f.ctypes.data, out.ctypes.data
+    assert L.rt_box_test_batch(0, p, p, p, None, None, -1, po) == RT_ERR_ARG
+    for bad in range(4):
+        a = [p, p, p, po]
+        a[bad] = None
+        assert L.rt_box_test_batch(0, a[0], a[1], a[2], None, None, 1, a[3]) == RT_ERR_ARG, bad
+    assert "bad args" in L.rt_last_error().decode()

@@ -18,6 +18,7 @@ import json
 import numpy as np
 import pytest
 
+import ray_batches as rb
 from conftest import GOLDEN, G_SCENES, golden_array, golden_meta, hexv, host_scene, oracle_camera
 from oracle import pyoracle as orc
 
@@ -921,3 +922,32 @@ def test_record_rules_parity(name, wide4, frustum, tune):
     assert np.array_equal(ht.reshape(-1).view(np.uint32),
                           golden_array(name, "hitt.f32.gz", np.float32).view(np.uint32))
     _check_fb(rgb, golden_array(name, "fb.f32.gz", np.float32))
+
+
+@pytest.mark.parametrize("kind", rb.VARIANTS)
+@pytest.mark.parametrize("base", rb.VARIANT_BASES)
+def test_frames_at_other_magnitudes(base, kind):
+    """48x32, 4-spp frames at depth 1 and 2 of the scenes of ray_batches.variant_arrays (scaled by
+    2^-10 and 2^12; shifted by 4096 in x, where vertices coincide and boxes go flat; with a
+    triangle at 2^100, where the frustum family has no bound on x and the float box filter is
+    off) against the oracle with the camera moved the same way: hits, t and rgb bit for bit, the
+    WAVE and LANE kernels over the 4-ary and the binary records.  (The oracle's frames are finite
+    on every one of them, the 2^100 scene included, so none drops its rgb check.)"""
+    a = rb.variant_arrays(base, kind)
+    cam = a["camera"](48, 32)
+    ds = rt.DeviceScene(a["P"], a["nodes"], a["aabbs"], a["tris"], a["triobj"], a["mats"], a["lights"], 0)
+    try:
+        for depth in (1, 2):
+            ref, rhi, rht = orc.render_g(a["P"], oracle_camera(cam), a["nodes"], a["aabbs"], a["tris"], a["triobj"],
+                                         a["mats"], a["lights"], spp=4, max_depth=depth, aov=True)
+            assert (rhi >= 0).mean() > 0.1 and np.isfinite(ref).all()
+            for kernel in KERNELS:
+                for flags in (0, BIN):
+                    rgb, hi, ht = ds.render(cam, spp=4, max_depth=depth, aov=True, kernel=kernel, flags=flags)
+                    what = (base, kind, depth, kernel, flags)
+                    assert np.array_equal(hi, rhi), what
+                    assert np.array_equal(ht.view(np.uint32), rht.view(np.uint32)), what
+                    assert np.array_equal(np.asarray(rgb, np.float32).view(np.uint32), ref.view(np.uint32)), what
+        assert ds.faults() == 0
+    finally:
+        ds.close()

@@ -76,7 +76,10 @@ def occlusion_case(name):
     2t, 1e-4, FLT_MAX] (t itself and its successor pin the strict <), miss ray i over
     [0, 1, FLT_MAX]; expected = hit and t < max_t."""
     b = rb.batch(name)
-    idx, t = b["idx"], b["t"]
+    return occlusion_from(b["idx"], b["t"])
+
+
+def occlusion_from(idx, t):
     i = np.arange(idx.size)
     up = np.nextafter(t, np.float32(np.inf), dtype=np.float32)
     hit_cycle = np.stack([np.float32(0.5) * t, t, up, np.float32(2.0) * t, np.full_like(t, 1e-4), np.full_like(t, FLT_MAX)])
@@ -217,3 +220,27 @@ def test_degenerate_rays_terminate_and_write():
         assert rc == 0 and (occ[:256] == 0).all() and (occ[256:] == SENT_I).all()
         rc, occ, _ = raw_trace(ds, L.RT_RAYS_OCCLUDED, rays, np.full(256, FLT_MAX, np.float32), 256, flags, with_t=False)
         assert rc == 0 and np.array_equal(occ[finite] != 0, want_idx >= 0) and (occ[nan] != SENT_I).all()
+
+
+@pytest.mark.parametrize("flags", [0, BINARY], ids=["wide", "binary"])
+@pytest.mark.parametrize("kind", rb.VARIANTS)
+@pytest.mark.parametrize("base", rb.VARIANT_BASES)
+def test_other_magnitudes(base, kind, flags):
+    """Closest hit and occlusion on the scenes of ray_batches.variant_arrays (scaled by 2^-10 and
+    2^12, shifted by 4096, with a triangle at 2^100 that takes the float box filter away): every
+    box decision at magnitudes the shipped scenes do not have, against the oracle ray by ray."""
+    a = rb.variant_arrays(base, kind)
+    ds = rt.DeviceScene(a["P"], a["nodes"], a["aabbs"], a["tris"], a["triobj"], a["mats"], a["lights"], 0)
+    try:
+        idx, t = ds.trace_rays(a["rays"], flags=flags)
+        bad = np.flatnonzero((idx != a["idx"]) | (bits(t) != bits(a["t"])))
+        print(f"{base} {kind} flags {flags}: {int((idx >= 0).sum())} hits, {bad.size} differ")
+        assert bad.size == 0, (bad[:8], idx[bad[:8]], a["idx"][bad[:8]], t[bad[:8]], a["t"][bad[:8]])
+        assert (a["idx"] >= 0).sum() > 100
+        max_t, want = occlusion_from(a["idx"], a["t"])
+        got = ds.trace_rays(a["rays"], mode="occluded", max_t=max_t, flags=flags)
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, (bad[:8], a["t"][bad[:8]], max_t[bad[:8]])
+        assert ds.faults() == 0
+    finally:
+        ds.close()
