@@ -27,7 +27,10 @@ extern "C" {
 
 #define RT_ABI_VERSION 3  /* 2: rt_renderer_opts.host_frame_name, RT_GATHER_HOST_SHARED;
                               3: RT_ERR_INTERNAL, rt_scene_faults, rt_tuning_* (RT_TUNE_*) in place of
-                                 environment variables, frame pairs, the resident HW1 scene */
+                                 environment variables, frame pairs, the resident HW1 scene;
+                                 added since without a new version (new entry points only, nothing
+                                 existing changed): rt_shade_opts, rt_shade_opts_default,
+                                 rt_shade_rays, rt_shade_rays_device, rt_shade_rays_variant */
 
 enum {
     RT_OK = 0,
@@ -495,6 +498,49 @@ int rt_trace_rays(rt_scene* s, int mode, const rt_ray* rays, const float* max_t,
  * the deep kernels (rt_scene_traversal_info) or whose per-lane stack does not fit LDS, else WIDE
  * (4-ary records, per-lane stack in LDS) or, with RT_FLAG_BINARY, BINARY. */
 int rt_trace_rays_variant(const rt_scene* s);
+
+/* ---- radiance queries on a resident scene -------------------------------------------------
+ * The reference's ray-level entry point for caller rays: radiance[3i..3i+2] =
+ *   TraceRayIterative(Ray(origin_i, direction_i), max_depth, miss_color, ..., rng_state = seeds[i],
+ *                     diffuse_bounce)                                  (G/include/query.h:156-220)
+ * bit for bit, the final clamp to [0, 1] included: one path per GPU lane with ShadeDirect's direct
+ * lighting and hard shadow rays (G/include/shader.h:44-110), the diffuse / mirror bounce and the
+ * throughput cut-off.  seeds == NULL: 42u for every ray, the reference's default argument.  The
+ * direction is used as given, as the reference uses primaryRay, and normalised only where the
+ * reference normalises it (unit_vector(ray.direction()) in the mirror branch).  Results are pinned
+ * against the reference for unit-length directions only.
+ * hit_idx / hit_t (each may be NULL): SearchBVH's result for the first segment, in rt_trace_rays'
+ *   conventions (-1 / -1.0f on a miss).  max_depth <= 0: radiance 0, -1 / -1.0f, no ray is traced
+ *   (query.h:172).
+ * opt->flags: RT_FLAG_BINARY or 0, as for rt_trace_rays; any other bit is RT_ERR_ARG.  A null
+ *   scene, rays, opt or radiance is RT_ERR_ARG; n > 2^31-1 is RT_ERR_UNSUPPORTED; n == 0 is RT_OK
+ *   with no launch.  Every argument check runs before any HIP call.
+ * Like a query, a shade call reads only the scene's immutable arrays, takes no part in the frame
+ * ordering and may run on any stream, from any thread, beside frames of the same scene, of a clone
+ * or of an rt_renderer's scene.  For any float bit patterns it terminates (at most max_depth
+ * segments, each a DFS that visits a node at most once) and writes every output.
+ * (Additive to ABI 3: rt_shade_opts, rt_shade_opts_default, rt_shade_rays, rt_shade_rays_device,
+ * rt_shade_rays_variant.) */
+typedef struct {
+    int32_t max_depth;        /* TraceRayIterative's maxDepth */
+    int32_t diffuse_bounce;
+    rt_vec3 miss_color;
+    int32_t flags;            /* RT_FLAG_BINARY or 0 */
+} rt_shade_opts;
+void rt_shade_opts_default(rt_shade_opts* o);   /* 1, 1, (0,0,0), 0 */
+
+/* Asynchronous on hip_stream (NULL = the null stream); device pointers on the scene's device:
+ * rays_dev n rt_ray, seeds_dev n (or NULL), radiance_dev 3n, hit_idx_dev / hit_t_dev n (or NULL). */
+int rt_shade_rays_device(rt_scene* s, const rt_ray* rays_dev, const uint32_t* seeds_dev, size_t n,
+                         const rt_shade_opts* opt, float* radiance_dev, int32_t* hit_idx_dev, float* hit_t_dev,
+                         void* hip_stream);
+/* Host arrays; uploads, shades, downloads, synchronises.  kernel_ms (may be NULL): HIP-event time
+ * of the kernel. */
+int rt_shade_rays(rt_scene* s, const rt_ray* rays, const uint32_t* seeds, size_t n, const rt_shade_opts* opt,
+                  float* radiance, int32_t* hit_idx, float* hit_t, float* kernel_ms);
+/* RT_RAYS_VARIANT_* of the latest rt_shade_rays[_device] call on s (NONE before the first), by
+ * rt_trace_rays_variant's rule; a word of its own, which rt_trace_rays does not write. */
+int rt_shade_rays_variant(const rt_scene* s);
 
 /* The Blinn-Phong powf of the kernels (restatement of the reference libm's powf, see
  * csrc/rt_math.hpp): rt_powf_host evaluates the host build, rt_powf_batch the device build

@@ -113,6 +113,10 @@ class RenderOpts(C.Structure):
                 ("tile_order", C.c_int32), ("flags", C.c_int32)]
 
 
+class ShadeOpts(C.Structure):
+    _fields_ = [("max_depth", C.c_int32), ("diffuse_bounce", C.c_int32), ("miss_color", Vec3), ("flags", C.c_int32)]
+
+
 class RendererOpts(C.Structure):
     _fields_ = [("n_devices", C.c_int32), ("devices", C.c_void_p), ("world_size", C.c_int32),
                 ("rank0", C.c_int32), ("unique_id", C.c_void_p), ("band_rows", C.c_int32),
@@ -187,6 +191,10 @@ SIGNATURES = {
     "rt_trace_rays_device": (I, [P, I, P, P, SZ, I, P, P, P]),
     "rt_trace_rays": (I, [P, I, P, P, SZ, I, P, P, P]),
     "rt_trace_rays_variant": (I, [P]),
+    "rt_shade_opts_default": (None, [P]),
+    "rt_shade_rays_device": (I, [P, P, P, SZ, P, P, P, P, P]),
+    "rt_shade_rays": (I, [P, P, P, SZ, P, P, P, P, P]),
+    "rt_shade_rays_variant": (I, [P]),
     "rt_powf_host": (C.c_float, [C.c_float, C.c_float]),
     "rt_debug_frustum_records": (C.c_int, [C.c_size_t, P, P, C.c_int, C.c_int, P, P, C.c_size_t]),
     "rt_debug_scene_pack": (I, [SZ, P, P, P, P, P]),

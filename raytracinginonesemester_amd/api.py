@@ -403,6 +403,76 @@ class DeviceScene:
         """The traversal the latest trace_rays call launched (RT_RAYS_VARIANT_*)."""
         return int(lib().rt_trace_rays_variant(self._handle()))
 
+    def shade_rays(self, rays, seeds=None, max_depth: int = 1, diffuse_bounce: bool = True, miss_color=(0, 0, 0),
+                   flags: int = 0, aov: bool = False, stream: Optional[int] = None, timing: bool = False):
+        """Radiance of caller rays (rt_shade_rays / rt_shade_rays_device): per ray the reference's
+        TraceRayIterative (G/include/query.h:156-220) with ``rng_state = seeds[i]`` (uint32, n; None:
+        42 for every ray), bit for bit, the final clamp included.  ``rays`` is (n, 6) float32, origin
+        then direction, the direction used as given (results are pinned for unit directions).
+
+        Returns ``radiance`` (n, 3) float32, or ``(radiance, idx, t)`` with ``aov=True``: the first
+        segment's SearchBVH result as trace_rays gives it (-1 / -1.0 on a miss or max_depth <= 0).
+
+        A numpy array takes the host path (upload, shade, download, synchronise; ``timing=True``
+        appends the kernel's HIP-event ms).  Torch tensors on the scene's device take the device
+        path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no
+        host synchronisation, tensors returned.  ``flags``: RT_FLAG_BINARY or 0."""
+        o = L.ShadeOpts()
+        o.max_depth, o.diffuse_bounce = int(max_depth), 1 if diffuse_bounce else 0
+        o.miss_color = _v3(miss_color)
+        o.flags = int(flags)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
+                raise ValueError(f"shade_rays: expects an (n, 6) float32 tensor on {dev}")
+            if timing:
+                raise ValueError("shade_rays: timing is measured on the host path only")
+            rays = rays.contiguous()
+            n = rays.shape[0]
+            sd = None
+            if seeds is not None:
+                if type(seeds).__module__.split(".")[0] == "torch":
+                    # (uint32 tensors have few torch ops: int32 tensors carry the same 32 bits)
+                    if seeds.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or seeds.device != dev:
+                        raise ValueError(f"shade_rays: seeds must be an int32 or uint32 tensor on {dev}")
+                    sd = seeds.contiguous()
+                else:
+                    sd = torch.from_numpy(_c(seeds, np.uint32).view(np.int32)).to(dev)
+                if tuple(sd.shape) != (n,):
+                    raise ValueError("shade_rays: seeds must hold one uint32 per ray")
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            rad = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            idx = torch.empty(n, dtype=torch.int32, device=dev) if aov else None
+            t = torch.empty(n, dtype=torch.float32, device=dev) if aov else None
+            check(lib().rt_shade_rays_device(self._handle(), rays.data_ptr(), None if sd is None else sd.data_ptr(), n,
+                                             C.byref(o), rad.data_ptr(), None if idx is None else idx.data_ptr(),
+                                             None if t is None else t.data_ptr(), stream))
+            return (rad, idx, t) if aov else rad
+        r = _c(rays, np.float32)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("shade_rays: expects an (n, 6) array of origins and directions")
+        n = r.shape[0]
+        sd = None
+        if seeds is not None:
+            sd = _c(seeds, np.uint32)
+            if sd.shape != (n,):
+                raise ValueError("shade_rays: seeds must hold one uint32 per ray")
+        rad = np.zeros((n, 3), np.float32)
+        idx = np.zeros(n, np.int32) if aov else None
+        t = np.zeros(n, np.float32) if aov else None
+        ms = C.c_float(0.0)
+        check(lib().rt_shade_rays(self._handle(), ptr(r), ptr(sd), n, C.byref(o), ptr(rad), ptr(idx), ptr(t),
+                                  C.byref(ms) if timing else None))
+        out = (rad, idx, t) if aov else rad
+        return (out, ms.value) if timing else out
+
+    def shade_rays_variant(self) -> int:
+        """The traversal the latest shade_rays call launched (RT_RAYS_VARIANT_*)."""
+        return int(lib().rt_shade_rays_variant(self._handle()))
+
     def faults(self, clear: bool = True) -> int:
         """RT_FAULT_* bits the device guards raised since the last clear (rt_scene_faults)."""
         f = C.c_uint32()

@@ -34,7 +34,7 @@
 //   rt_traverse.hpp    the traversals (wave DFS, frustum, lane, LDS, deep)
 //   rt_shade.hpp       hit resolution, materials, camera ray, shading, bounces, trace_sample
 //   rt_prepass.hpp     tile bounds, root and tree-cut culling passes, work lists
-//   rt_query.hpp       batched ray queries on a resident scene (rt_trace_rays*)
+//   rt_query.hpp       batched ray queries on a resident scene (rt_trace_rays*, rt_shade_rays*)
 // Separate translation units: rt_scene_pack.cpp (the host half of rt_scene_create: checks, ids,
 // stack bounds, every packed array), rt_records.cpp (host record builders), rt_hw1.hip (the HW1
 // path), rt_frame.hip, rt_lbvh.hip, rt_renderer.hip.
@@ -660,6 +660,8 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     // RT_RAYS_VARIANT_* of the latest rt_trace_rays[_device] call (queries run beside frames,
     // from any thread: the one scene field they write)
     std::atomic<int> query_variant{RT_RAYS_VARIANT_NONE};
+    // ... and of the latest rt_shade_rays[_device] call, a word of its own for the same reason
+    std::atomic<int> shade_variant{RT_RAYS_VARIANT_NONE};
     DevBuf inode, wnode, ibox, leaf, tnorm, objids, mats, lights, jitter;
     DevBuf fnode;    // 2^f_log2-ary records of the frustum traversal (empty: it takes wnode's 4-ary ones)
     DevBuf qent, qhdr;  // fnode quantised (build_quant_records): the big-scene kernels' records
@@ -1670,6 +1672,108 @@ extern "C" int rt_trace_rays(rt_scene* s, int mode, const rt_ray* rays, const fl
 
 extern "C" int rt_trace_rays_variant(const rt_scene* s) {
     return s ? s->query_variant.load(std::memory_order_relaxed) : RT_RAYS_VARIANT_NONE;
+}
+
+// ---- radiance queries (rt_query.hpp, shade_rays_kernel) ----------------------------------------
+extern "C" void rt_shade_opts_default(rt_shade_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->max_depth = 1;
+    o->diffuse_bounce = 1;
+}
+
+namespace {
+// As trace_rays_args: no HIP call and no read through s before the checks pass.
+int shade_rays_args(const rt_scene* s, const void* rays, size_t n, const rt_shade_opts* opt, const float* radiance) {
+    if (!s) return set_error(RT_ERR_ARG, "rt_shade_rays: null scene");
+    if (!opt) return set_error(RT_ERR_ARG, "rt_shade_rays: null opts");
+    if (opt->flags & ~RT_FLAG_BINARY) return set_error(RT_ERR_ARG, "rt_shade_rays: unknown flag");
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_shade_rays: more than 2^31-1 rays in one batch");
+    if (!rays || !radiance) return set_error(RT_ERR_ARG, "rt_shade_rays: null rays or radiance");
+    return RT_OK;
+}
+
+// One launch on st under trace_rays_launch's variant rule; of the scene it writes shade_variant alone.
+int shade_rays_launch(rt_scene* s, const rt_ray* rays, const uint32_t* seeds, size_t n, const rt_shade_opts& opt,
+                      float* radiance, int32_t* hit_idx, float* hit_t, hipStream_t st) {
+    int variant = RT_RAYS_VARIANT_DEEP;
+    if (!s->deep) {
+        if (s->wide && s->lane_wide && !(opt.flags & RT_FLAG_BINARY)) variant = RT_RAYS_VARIANT_WIDE;
+        else if (s->lane_stack) variant = RT_RAYS_VARIANT_BINARY;
+    }
+    if (s->deep && !s->tri.p) return set_error(RT_ERR_INTERNAL, "rt_shade_rays: a deep scene without its triangle array");
+    ShadeParams S;
+    std::memset(&S, 0, sizeof(S));
+    S.sc = scene_view(s);  // (the packed records and the shading tables; no frustum or cut array is read)
+    S.sc.wide = variant == RT_RAYS_VARIANT_WIDE ? 1 : 0;
+    S.sc.f_log2 = 2;
+    S.sc.ncut = 0;
+    S.rays = reinterpret_cast<const float*>(rays);
+    S.seeds = seeds;
+    S.n = uint32_t(n);
+    S.max_depth = opt.max_depth;
+    S.diffuse_bounce = opt.diffuse_bounce;
+    S.miss = mk(opt.miss_color.x, opt.miss_color.y, opt.miss_color.z);
+    S.radiance = radiance;
+    S.hit_idx = hit_idx;
+    S.hit_t = hit_t;
+    const dim3 grid((S.n + BLOCK - 1) / BLOCK), block(BLOCK);
+    if (variant == RT_RAYS_VARIANT_WIDE) hipLaunchKernelGGL((shade_rays_kernel<RT_RAYS_VARIANT_WIDE>), grid, block, 0, st, S);
+    else if (variant == RT_RAYS_VARIANT_BINARY) hipLaunchKernelGGL((shade_rays_kernel<RT_RAYS_VARIANT_BINARY>), grid, block, 0, st, S);
+    else hipLaunchKernelGGL((shade_rays_kernel<RT_RAYS_VARIANT_DEEP>), grid, block, 0, st, S);
+    HIP_TRY(hipGetLastError());
+    s->shade_variant.store(variant, std::memory_order_relaxed);
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_shade_rays_device(rt_scene* s, const rt_ray* rays, const uint32_t* seeds, size_t n,
+                                    const rt_shade_opts* opt, float* radiance, int32_t* hit_idx, float* hit_t,
+                                    void* stream) {
+    const int rc = shade_rays_args(s, rays, n, opt, radiance);
+    if (rc != RT_OK || n == 0) return rc;
+    DeviceGuard g(s->device);
+    return shade_rays_launch(s, rays, seeds, n, *opt, radiance, hit_idx, hit_t, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rt_shade_rays(rt_scene* s, const rt_ray* rays, const uint32_t* seeds, size_t n, const rt_shade_opts* opt,
+                             float* radiance, int32_t* hit_idx, float* hit_t, float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.0f;
+    int rc = shade_rays_args(s, rays, n, opt, radiance);
+    if (rc != RT_OK || n == 0) return rc;
+    DeviceGuard g(s->device);
+    DevBuf dr, ds, dc, di, dt;
+    if ((rc = dr.upload(rays, n * sizeof(rt_ray))) != RT_OK) return rc;
+    if (seeds && (rc = ds.upload(seeds, n * sizeof(uint32_t))) != RT_OK) return rc;
+    if ((rc = dc.alloc(3 * n * sizeof(float))) != RT_OK) return rc;
+    if (hit_idx && (rc = di.alloc(n * sizeof(int32_t))) != RT_OK) return rc;
+    if (hit_t && (rc = dt.alloc(n * sizeof(float))) != RT_OK) return rc;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } ev;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, nullptr));
+    }
+    rc = shade_rays_launch(s, static_cast<const rt_ray*>(dr.p), static_cast<const uint32_t*>(ds.p), n, *opt,
+                           static_cast<float*>(dc.p), static_cast<int32_t*>(di.p), static_cast<float*>(dt.p), nullptr);
+    if (rc != RT_OK) return rc;
+    if (kernel_ms) HIP_TRY(hipEventRecord(ev.b, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    HIP_TRY(hipMemcpy(radiance, dc.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (hit_idx) HIP_TRY(hipMemcpy(hit_idx, di.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (hit_t) HIP_TRY(hipMemcpy(hit_t, dt.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_shade_rays_variant(const rt_scene* s) {
+    return s ? s->shade_variant.load(std::memory_order_relaxed) : RT_RAYS_VARIANT_NONE;
 }
 
 void rt::scene_set_caller_ordered(rt_scene* s, bool on) {

@@ -1,7 +1,8 @@
 // rt_query.hpp — batched ray queries on a resident scene (rt_trace_rays*, include/rt_mi355x.h):
 // closest hit = SearchBVH (G/include/query.h:224-311) for caller rays, occlusion = the decision
 // of IsInShadow (G/include/shader.h:59-61).  One ray per lane over the per-lane traversals of
-// rt_traverse.hpp; DESIGN.md §4.17.
+// rt_traverse.hpp; DESIGN.md §4.17.  Below them the radiance queries (rt_shade_rays*):
+// TraceRayIterative (G/include/query.h:156-220) for caller rays, one path per lane; §4.18.
 // Part of rt_device.hip's translation unit, included inside its anonymous namespace after rt_shade.hpp.
 #pragma once
 
@@ -45,4 +46,124 @@ __global__ __launch_bounds__(BLOCK) void trace_rays_kernel(QueryParams Q) {
         Q.hit_idx[i] = hit ? leaf_tri<!LDS>(Q.sc, hs.slot) : -1;
         if (Q.hit_t != nullptr) Q.hit_t[i] = hit ? hs.bestT : -1.0f;
     }
+}
+
+// ---- radiance queries (rt_shade_rays*): TraceRayIterative for caller rays, DESIGN.md §4.18 ----
+struct ShadeParams {
+    SceneView sc;
+    const float* __restrict__ rays;     // n x rt_ray
+    const uint32_t* __restrict__ seeds;  // n rng states, or null: 42u each (query.h:169)
+    uint32_t n;
+    int32_t max_depth, diffuse_bounce;
+    f3 miss;
+    float* __restrict__ radiance;  // 3n
+    int32_t* __restrict__ hit_idx;  // the first segment's SearchBVH result; may be null
+    float* __restrict__ hit_t;      // may be null
+};
+
+// The variant's per-lane traversal (the three of trace_rays_kernel).
+template <int VARIANT>
+__device__ __forceinline__ void shade_traverse(const SceneView& sc, const RayPre& r, bool any_hit, float any_hit_dist,
+                                               HitState& hs, uint32_t* stk) {
+    if constexpr (VARIANT == RT_RAYS_VARIANT_WIDE) traverse_lane_lds_wide(sc, r, true, any_hit, any_hit_dist, hs, stk);
+    else if constexpr (VARIANT == RT_RAYS_VARIANT_BINARY) traverse_lane_lds(sc, r, true, any_hit, any_hit_dist, hs, stk);
+    else traverse_deep(sc, r, true, any_hit, any_hit_dist, hs);
+}
+
+// One path per lane: TraceRayIterative (query.h:156-220) as written, with ShadeDirect
+// (shader.h:65-110) and IsInShadow (shader.h:44-62) inside its depth loop.  The shading copies
+// of rt_shade.hpp keep a wave together (every lane enters every traversal, masked); here nothing
+// is wave-wide, so a lane takes the reference's own control flow: `continue` past a light that
+// faces away, `break` on a miss, on kd + kr <= 0 and on a spent throughput, and it leaves when
+// its path ends.  The lane's LDS stack serves its traversals one after another (each starts
+// empty): the path segment of a depth, then one shadow ray per light.  A shadow ray is an
+// any-hit query bounded by the light's distance (IsInShadow reads only `hit && t < dist`).
+// The bounce of the last depth has no effect (its ray is never traced, its draws are never
+// read) and is skipped, as in trace_sample.
+template <int VARIANT>
+__global__ __launch_bounds__(BLOCK) void shade_rays_kernel(ShadeParams S) {
+    constexpr bool LDS = VARIANT != RT_RAYS_VARIANT_DEEP;
+    __shared__ uint32_t stk_all[LDS ? LANE_LDS_CAP * BLOCK : 1];
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;  // n < 2^31
+    if (i >= S.n) return;
+    uint32_t* stk = stk_all + (LDS ? threadIdx.x : 0);
+    const SceneView& sc = S.sc;
+    const float* R = S.rays + 6 * (size_t)i;
+    RayPre ray = make_ray(mk(R[0], R[1], R[2]), mk(R[3], R[4], R[5]), scene_bmax(sc));  // the direction as given
+    uint32_t rng = S.seeds != nullptr ? S.seeds[i] : 42u;
+    f3 radiance = mk(0.f, 0.f, 0.f);
+    f3 thr = mk(1.f, 1.f, 1.f);
+    const int max_depth = S.max_depth;
+    if (max_depth <= 0) {  // query.h:172: no ray is traced
+        if (S.hit_idx != nullptr) S.hit_idx[i] = -1;
+        if (S.hit_t != nullptr) S.hit_t[i] = -1.0f;
+    }
+    for (int depth = 0; depth < max_depth; ++depth) {
+        HitState hs;
+        shade_traverse<VARIANT>(sc, ray, false, 0.0f, hs, stk);
+        const bool hit = hs.slot >= 0;
+        if (depth == 0) {  // written at once: nothing of it stays live across the shading
+            if (S.hit_idx != nullptr) S.hit_idx[i] = hit ? leaf_tri<!LDS>(sc, hs.slot) : -1;
+            if (S.hit_t != nullptr) S.hit_t[i] = hit ? hs.bestT : -1.0f;
+        }
+        if (!hit) {
+            radiance = add(radiance, mul(thr, S.miss));
+            break;
+        }
+        const SurfHit sh = resolve_hit<!LDS>(sc, ray, hs.slot);
+        // ShadeDirect (shader.h:65-110)
+        const f3 N = unit(sh.n);
+        const f3 V = unit(sub(ray.o, sh.p));
+        f3 Lo = mk(0.f, 0.f, 0.f);
+        {
+            const DevMaterial m = material_of(sc, sh.tri);
+            Lo = add(Lo, scale(mk(m.albedo[0], m.albedo[1], m.albedo[2]), 0.05f));
+            Lo = add(Lo, mk(m.emission[0], m.emission[1], m.emission[2]));
+        }
+        for (int li = 0; li < sc.num_lights; ++li) {
+            const DevLight& lt = sc.lights[li];
+            const f3 lpos = mk(lt.pos[0], lt.pos[1], lt.pos[2]);
+            const f3 L = unit(sub(lpos, sh.p));
+            const float NdotL = fmaxf(dot(N, L), 0.0f);
+            if (NdotL <= 0.0f) continue;
+            // IsInShadow (shader.h:44-62)
+            const f3 toL = sub(lpos, sh.p);
+            const float dist = sqrtf(dot(toL, toL));
+            if (dist > 0.0f) {
+                const RayPre sray = make_ray(add(sh.p, scale(N, RT_EPS)), divf(toL, dist), scene_bmax(sc));
+                HitState shs;
+                shade_traverse<VARIANT>(sc, sray, true, dist, shs, stk);
+                if (shs.slot >= 0 && shs.bestT < dist) continue;
+            }
+            // the light's term, once its shadow ray is known to be clear
+            const DevMaterial m = material_of(sc, sh.tri);
+            const f3 f = eval_brdf(m, sh.n, V, L);
+            const f3 rad = scale(mk(lt.color[0], lt.color[1], lt.color[2]), (float)lt.intensity);
+            Lo = add(Lo, scale(mul(rad, f), NdotL));
+        }
+        radiance = add(radiance, mul(thr, Lo));
+        if (depth + 1 >= max_depth) break;
+        // bounce (query.h:193-216)
+        const DevMaterial m = material_of(sc, sh.tri);
+        const float kd = m.kd, kr = m.kr, total = kd + kr;
+        if (total <= 0.0f) break;
+        const float xi = rng_next(rng);
+        if (S.diffuse_bounce && xi < kd / total) {
+            f3 dd = random_unit_vector(rng);
+            if (!(dot(dd, N) > 0.0f)) dd = mk(-dd.x, -dd.y, -dd.z);
+            const float nl = fmaxf(dot(N, dd), 0.0f);
+            ray = make_ray(add(sh.p, scale(N, RT_EPS)), dd, scene_bmax(sc));
+            thr = mul(thr, scale(mk(m.albedo[0], m.albedo[1], m.albedo[2]), 2.0f * nl));
+        } else {
+            const f3 I = unit(ray.d);
+            const f3 refl = sub(I, scale(N, 2.0f * dot(I, N)));
+            ray = make_ray(add(sh.p, scale(N, RT_EPS)), refl, scene_bmax(sc));
+            thr = mul(thr, scale(mk(m.spec[0], m.spec[1], m.spec[2]), kr));
+        }
+        if (thr.x < 1e-4f && thr.y < 1e-4f && thr.z < 1e-4f) break;
+    }
+    const f3 c = clamp01(radiance);
+    S.radiance[3 * (size_t)i] = c.x;
+    S.radiance[3 * (size_t)i + 1] = c.y;
+    S.radiance[3 * (size_t)i + 2] = c.z;
 }
