@@ -30,7 +30,9 @@ extern "C" {
                                  environment variables, frame pairs, the resident HW1 scene;
                                  added since without a new version (new entry points only, nothing
                                  existing changed): rt_shade_opts, rt_shade_opts_default,
-                                 rt_shade_rays, rt_shade_rays_device, rt_shade_rays_variant */
+                                 rt_shade_rays, rt_shade_rays_device, rt_shade_rays_variant; rt_hit,
+                                 rt_trace_hits, rt_trace_hits_device, rt_trace_hits_variant,
+                                 rt_hit_record_host, rt_camera_rays_host, rt_camera_rays_device */
 
 enum {
     RT_OK = 0,
@@ -541,6 +543,69 @@ int rt_shade_rays(rt_scene* s, const rt_ray* rays, const uint32_t* seeds, size_t
 /* RT_RAYS_VARIANT_* of the latest rt_shade_rays[_device] call on s (NONE before the first), by
  * rt_trace_rays_variant's rule; a word of its own, which rt_trace_rays does not write. */
 int rt_shade_rays_variant(const rt_scene* s);
+
+/* ---- hit records on a resident scene -------------------------------------------------------
+ * Between the two queries above: for caller rays, the whole HitRecord that
+ * SearchBVH returns (G/include/query.h:224-311 with intersectTriangle's tail, :110-130) and the
+ * ids assignMaterialToHit reads (:134-153), bit for bit, for callers that shade for themselves
+ * (G-buffers, texture lookups, picking with a normal, baking, a BRDF of their own).
+ * rt_trace_hits follows rt_trace_rays in RT_RAYS_CLOSEST mode in every convention: the direction is
+ *   used as given, tmin = 1e-4, the same tie rule, deep-tree overflow rule and brute-force
+ *   completion, so tri and t are rt_trace_rays' hit_idx and hit_t.  A miss writes tri = -1,
+ *   t = -1.0f and zero in every other field; every byte of every record is written.
+ * flags: RT_FLAG_BINARY or 0; any other bit is RT_ERR_ARG.  n == 0 is RT_OK with no launch;
+ *   n > 2^31-1 is RT_ERR_UNSUPPORTED.  A null scene, rays or hits is RT_ERR_ARG, and so is a
+ *   hits_dev that is not 16-byte aligned (the kernel stores 16-byte words; the host entry's
+ *   `hits` needs no alignment).  Every argument check runs before any HIP call.
+ * Like a query it reads only the scene's immutable arrays and takes no part in the frame ordering:
+ * any stream, any thread, beside frames of the same scene, of a clone or of an rt_renderer's
+ * scene.  For any float bit patterns in rays it terminates and writes every record; the results
+ * are specified for finite rays only.
+ * (Additive to ABI 3: rt_hit, rt_trace_hits, rt_trace_hits_device, rt_trace_hits_variant,
+ * rt_hit_record_host, rt_camera_rays_host, rt_camera_rays_device.) */
+typedef struct {            /* 64 bytes, this library's own layout */
+    int32_t tri;            /* triangle index; -1: miss */
+    float   t, u, v;        /* intersectTriangle's t, u, v (query.h:92-104) */
+    rt_vec3 p;              /* rec.p = origin + direction * t */
+    rt_vec3 normal;         /* rec.normal: the shading normal of query.h:119-128 */
+    rt_vec3 geom_normal;    /* geomN of query.h:115-117, after the flip towards the ray */
+    int32_t front_face;     /* rec.front_face, 0 / 1 */
+    int32_t object_id;      /* triObjectIds[tri] as stored (-1 when the scene has none) */
+    int32_t material;       /* the index assignMaterialToHit takes (query.h:149-152), -1: Material() defaults */
+} rt_hit;
+
+/* Asynchronous on hip_stream (NULL = the null stream); device pointers on the scene's device:
+ * rays_dev n rt_ray, hits_dev n rt_hit (16-byte aligned). */
+int rt_trace_hits_device(rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, rt_hit* hits_dev, void* hip_stream);
+/* Host arrays; uploads, traces, downloads, synchronises.  kernel_ms (may be NULL): HIP-event time
+ * of the kernel. */
+int rt_trace_hits(rt_scene* s, const rt_ray* rays, size_t n, int flags, rt_hit* hits, float* kernel_ms);
+/* RT_RAYS_VARIANT_* of the latest rt_trace_hits[_device] call on s (NONE before the first), by
+ * rt_trace_rays_variant's rule; a word of its own, which the other queries do not write. */
+int rt_trace_hits_variant(const rt_scene* s);
+
+/* Host build of the record's arithmetic (no device needed, like rt_powf_host): out[i] =
+ * intersectTriangle(rays[i], tris[i], 1e-4f, FLT_MAX) as a full record, through the functions the
+ * kernel runs.  tri = i on a hit, object_id = material = -1; a miss record otherwise. */
+int rt_hit_record_host(const rt_ray* rays, const rt_triangle* tris, int n, rt_hit* out);
+
+/* Camera rays of image rows [row0, row0 + rows): the rays render() shoots and the rng states it
+ * gives them (G/include/query.cu:146-158), for rt_trace_rays / rt_trace_hits / rt_shade_rays.  The
+ * ray of sample s of pixel (x, y) is at index ((y - row0) * W + x) * spp + s, the order of the
+ * reference's AOVs: origin = cam->center, direction = unit_vector(pix - center) with
+ * pix = (p00 + du * (float(x) + jx)) + dv * (float(y) + jy) as Camera::get_ray computes it, its
+ * double division included (camera.h:49-53, 218-223); seeds[i] = make_rng_seed(x, y, s)
+ * (query.h:44-48) with the absolute y.  jitter: 2*spp floats (jx, jy per sample); seeds may be NULL.
+ * spp < 1, rows outside the image or a null camera or rays is RT_ERR_ARG; W * rows * spp > 2^31-1
+ * is RT_ERR_UNSUPPORTED; rows == 0 is RT_OK and writes nothing.
+ * rt_camera_rays_host needs no device; jitter == NULL means rt_jittered_samples(spp, 42, 1).
+ * rt_camera_rays_device: one launch on hip_stream of `device` (asynchronous); jitter_dev, rays_dev
+ * and seeds_dev are device pointers there, and a null jitter_dev is RT_ERR_ARG.  Every argument
+ * check runs before any HIP call. */
+int rt_camera_rays_host(const rt_camera* cam, int spp, const float* jitter, int row0, int rows, rt_ray* rays,
+                        uint32_t* seeds);
+int rt_camera_rays_device(int device, const rt_camera* cam, int spp, const float* jitter_dev, int row0, int rows,
+                          rt_ray* rays_dev, uint32_t* seeds_dev, void* hip_stream);
 
 /* The Blinn-Phong powf of the kernels (restatement of the reference libm's powf, see
  * csrc/rt_math.hpp): rt_powf_host evaluates the host build, rt_powf_batch the device build

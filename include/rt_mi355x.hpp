@@ -154,6 +154,27 @@ inline std::vector<int32_t> trace_occluded(const DeviceScene& ds, const std::vec
     return occ;
 }
 
+// The whole HitRecord of each ray's closest hit (rt_trace_hits): tri = -1, t = -1 on a miss.
+inline std::vector<rt_hit> trace_hits(const DeviceScene& ds, const std::vector<rt_ray>& rays, int flags = 0) {
+    std::vector<rt_hit> h(rays.size());
+    if (!rays.empty()) check(rt_trace_hits(ds.get(), rays.data(), rays.size(), flags, h.data(), nullptr));
+    return h;
+}
+// The camera rays of rows [row0, row0 + rows) as render() shoots them, sample s of pixel (x, y) at
+// ((y - row0) * W + x) * spp + s (rt_camera_rays_host; jitter: jittered_samples(spp, 42)); seeds,
+// if given, receives make_rng_seed(x, y, s) per ray.
+inline std::vector<rt_ray> camera_rays(const Camera& cam, int spp, int row0, int rows,
+                                       std::vector<uint32_t>* seeds = nullptr) {
+    if (spp < 1 || rows < 0) throw Error(RT_ERR_ARG, "camera_rays: spp < 1 or rows < 0");
+    const size_t n = size_t(cam.width()) * size_t(rows) * size_t(spp);
+    std::vector<rt_ray> rays(n ? n : 1);
+    if (seeds) seeds->assign(n ? n : 1, 0u);
+    check(rt_camera_rays_host(&cam.c, spp, nullptr, row0, rows, rays.data(), seeds ? seeds->data() : nullptr));
+    rays.resize(n);
+    if (seeds) seeds->resize(n);
+    return rays;
+}
+
 inline void write_p6(const std::string& path, const Framebuffer& fb, const rt_ppm_options* opt = nullptr) {
     check(rt_ppm_write(path.c_str(), fb.rgb.data(), fb.width, fb.height, opt));
 }

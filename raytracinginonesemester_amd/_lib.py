@@ -117,6 +117,16 @@ class ShadeOpts(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("diffuse_bounce", C.c_int32), ("miss_color", Vec3), ("flags", C.c_int32)]
 
 
+class Ray(C.Structure):
+    _fields_ = [("origin", Vec3), ("direction", Vec3)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("tri", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("p", Vec3),
+                ("normal", Vec3), ("geom_normal", Vec3), ("front_face", C.c_int32), ("object_id", C.c_int32),
+                ("material", C.c_int32)]
+
+
 class RendererOpts(C.Structure):
     _fields_ = [("n_devices", C.c_int32), ("devices", C.c_void_p), ("world_size", C.c_int32),
                 ("rank0", C.c_int32), ("unique_id", C.c_void_p), ("band_rows", C.c_int32),
@@ -195,6 +205,12 @@ SIGNATURES = {
     "rt_shade_rays_device": (I, [P, P, P, SZ, P, P, P, P, P]),
     "rt_shade_rays": (I, [P, P, P, SZ, P, P, P, P, P]),
     "rt_shade_rays_variant": (I, [P]),
+    "rt_trace_hits_device": (I, [P, P, SZ, I, P, P]),
+    "rt_trace_hits": (I, [P, P, SZ, I, P, P]),
+    "rt_trace_hits_variant": (I, [P]),
+    "rt_hit_record_host": (I, [P, P, I, P]),
+    "rt_camera_rays_host": (I, [P, I, P, I, I, P, P]),
+    "rt_camera_rays_device": (I, [I, P, I, P, I, I, P, P, P]),
     "rt_powf_host": (C.c_float, [C.c_float, C.c_float]),
     "rt_debug_frustum_records": (C.c_int, [C.c_size_t, P, P, C.c_int, C.c_int, P, P, C.c_size_t]),
     "rt_debug_scene_pack": (I, [SZ, P, P, P, P, P]),

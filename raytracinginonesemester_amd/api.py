@@ -30,6 +30,10 @@ from ._lib import check, lib, ptr
 LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("color", "<f4", 3), ("intensity", "<i4")])
 assert LIGHT_DTYPE.itemsize == C.sizeof(L.Light) == 28
 assert C.sizeof(L.Material) == 52 and C.sizeof(L.Triangle) == 72 and C.sizeof(L.AABB) == 24
+# rt_hit (include/rt_mi355x.h): one record of DeviceScene.trace_hits
+HIT_DTYPE = np.dtype([("tri", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("p", "<f4", 3), ("normal", "<f4", 3),
+                      ("geom_normal", "<f4", 3), ("front_face", "<i4"), ("object_id", "<i4"), ("material", "<i4")])
+assert HIT_DTYPE.itemsize == C.sizeof(L.Hit) == 64
 
 
 def _v3(v) -> L.Vec3:
@@ -473,6 +477,46 @@ class DeviceScene:
         """The traversal the latest shade_rays call launched (RT_RAYS_VARIANT_*)."""
         return int(lib().rt_shade_rays_variant(self._handle()))
 
+    def trace_hits(self, rays, flags: int = 0, stream: Optional[int] = None, timing: bool = False):
+        """Hit records of caller rays (rt_trace_hits / rt_trace_hits_device): per ray the HitRecord
+        SearchBVH returns (G/include/query.h:224-311, intersectTriangle's tail :110-130) with the ids
+        assignMaterialToHit reads, bit for bit.  ``rays`` is (n, 6) float32, origin then direction,
+        the direction used as given; ``tri`` and ``t`` are trace_rays' closest-hit answers.  A miss
+        is tri -1, t -1.0 and zero elsewhere.
+
+        A numpy array takes the host path and returns an (n,) array of HIT_DTYPE (``timing=True``
+        appends the kernel's HIP-event ms).  A torch tensor on the scene's device takes the device
+        path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no host
+        synchronisation, and one (n, 16) int32 tensor is returned, the records' 32-bit words
+        (hit_fields names them).  ``flags``: RT_FLAG_BINARY or 0."""
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
+                raise ValueError(f"trace_hits: expects an (n, 6) float32 tensor on {dev}")
+            if timing:
+                raise ValueError("trace_hits: timing is measured on the host path only")
+            rays = rays.contiguous()
+            n = rays.shape[0]
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            hits = torch.empty((n, 16), dtype=torch.int32, device=dev)
+            check(lib().rt_trace_hits_device(self._handle(), rays.data_ptr(), n, int(flags), hits.data_ptr(), stream))
+            return hits
+        r = _c(rays, np.float32)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("trace_hits: expects an (n, 6) array of origins and directions")
+        n = r.shape[0]
+        hits = np.zeros(n, HIT_DTYPE)
+        ms = C.c_float(0.0)
+        check(lib().rt_trace_hits(self._handle(), ptr(r), n, int(flags), ptr(hits), C.byref(ms) if timing else None))
+        return (hits, ms.value) if timing else hits
+
+    def trace_hits_variant(self) -> int:
+        """The traversal the latest trace_hits call launched (RT_RAYS_VARIANT_*)."""
+        return int(lib().rt_trace_hits_variant(self._handle()))
+
     def faults(self, clear: bool = True) -> int:
         """RT_FAULT_* bits the device guards raised since the last clear (rt_scene_faults)."""
         f = C.c_uint32()
@@ -739,6 +783,87 @@ def intersect_rays(triangle18, dirs, origin=(0.0, 0.0, 0.0), hw1: bool = True, t
     check(lib().rt_intersect_rays(int(device), C.byref(tri), _f3(origin), ptr(d), n, 1 if hw1 else 0,
                                   float(tmin), float(tmax), ptr(hit), ptr(t)))
     return hit, t
+
+
+def hit_record_host(rays, tris) -> np.ndarray:
+    """Host build of the hit record's arithmetic (rt_hit_record_host, no device): record i is
+    intersectTriangle(rays[i], tris[i], 1e-4, FLT_MAX) in full.  ``rays`` (n, 6), ``tris`` (n, 18)
+    float32 (v0, v1, v2, n0, n1, n2); returns (n,) HIT_DTYPE with tri = i on a hit, object_id and
+    material -1."""
+    r, t = _c(rays, np.float32), _c(tris, np.float32)
+    if r.ndim != 2 or r.shape[1] != 6 or t.shape != (r.shape[0], 18):
+        raise ValueError("hit_record_host: expects (n, 6) rays and (n, 18) triangles")
+    out = np.zeros(r.shape[0], HIT_DTYPE)
+    check(lib().rt_hit_record_host(ptr(r), ptr(t), r.shape[0], ptr(out)))
+    return out
+
+
+# rt_hit's 32-bit words by field: (first word, words, float)
+_HIT_WORDS = {"tri": (0, 1, False), "t": (1, 1, True), "u": (2, 1, True), "v": (3, 1, True), "p": (4, 3, True),
+              "normal": (7, 3, True), "geom_normal": (10, 3, True), "front_face": (13, 1, False),
+              "object_id": (14, 1, False), "material": (15, 1, False)}
+
+
+def hit_fields(hits) -> dict:
+    """Named views (no copies) of the (n, 16) int32 tensor DeviceScene.trace_hits returns on the
+    device path: int32 (n,) for tri, front_face, object_id and material, float32 (n,) for t, u and
+    v, float32 (n, 3) for p, normal and geom_normal."""
+    import torch
+
+    if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 16:
+        raise ValueError("hit_fields: expects the (n, 16) int32 tensor of trace_hits")
+    out = {}
+    for name, (w, k, is_float) in _HIT_WORDS.items():
+        v = hits[:, w] if k == 1 else hits[:, w:w + k]
+        out[name] = v.view(torch.float32) if is_float else v
+    return out
+
+
+def camera_rays(camera: Camera, spp: int = 1, jitter=None, row0: int = 0, rows: Optional[int] = None,
+                device: Optional[int] = None, stream: Optional[int] = None):
+    """The camera rays of image rows [row0, row0 + rows) (default: to the last row) and their rng
+    seeds, as render() makes them (rt_camera_rays_host / rt_camera_rays_device): ray
+    ((y - row0) * W + x) * spp + s is sample s of pixel (x, y), Camera::get_ray of
+    (x + jitter[s, 0], y + jitter[s, 1]); its seed is make_rng_seed(x, y, s).  ``jitter``: (spp, 2)
+    float32, None for jittered_samples(spp).
+
+    ``device=None``: the host build, numpy ``(rays (n, 6) float32, seeds (n,) uint32)``.  An int
+    device: one launch on ``stream`` of that device (a HIP stream handle; default torch's current
+    stream), torch tensors ``(rays (n, 6) float32, seeds (n,) int32)``, the seeds' 32 bits as
+    DeviceScene.shade_rays takes them; nothing passes through the host but the jitter table."""
+    spp = int(spp)
+    H = camera.pixel_height
+    if rows is None:
+        rows = H - int(row0)
+    n = max(camera.pixel_width * int(rows) * spp, 0) if 0 <= int(rows) <= H and spp >= 1 else 0
+    jit = None
+    if jitter is not None:
+        jit = _c(jitter, np.float32).reshape(-1)
+        if jit.size != 2 * spp:
+            raise ValueError("camera_rays: jitter must hold (spp, 2) floats")
+    if device is None:
+        rays = np.zeros((n, 6), np.float32)
+        seeds = np.zeros(n, np.uint32)
+        check(lib().rt_camera_rays_host(C.byref(camera.c), spp, ptr(jit), int(row0), int(rows), ptr(rays), ptr(seeds)))
+        return rays, seeds
+    import torch
+
+    dev = torch.device("cuda", int(device))
+    if jit is None:
+        jit = jittered_samples(spp).reshape(-1)
+    cur = torch.cuda.current_stream(dev)
+    jd = torch.from_numpy(jit).to(dev)  # on torch's current stream
+    # (an empty tensor has no address: one spare element keeps the C checks' answers the same)
+    rays = torch.empty((max(n, 1), 6), dtype=torch.float32, device=dev)[:n]
+    seeds = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    foreign = stream is not None and stream != cur.cuda_stream
+    if foreign:  # the table must be there before the launch is queued on the caller's stream
+        cur.synchronize()
+    check(lib().rt_camera_rays_device(int(device), C.byref(camera.c), spp, jd.data_ptr(), int(row0), int(rows),
+                                      rays.data_ptr(), seeds.data_ptr(), stream if foreign else cur.cuda_stream))
+    if foreign:  # ... and stay until that launch has read it
+        jd.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+    return rays, seeds
 
 
 def build_bvh(positions, indices):

@@ -662,6 +662,8 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     std::atomic<int> query_variant{RT_RAYS_VARIANT_NONE};
     // ... and of the latest rt_shade_rays[_device] call, a word of its own for the same reason
     std::atomic<int> shade_variant{RT_RAYS_VARIANT_NONE};
+    // ... and of the latest rt_trace_hits[_device] call
+    std::atomic<int> hits_variant{RT_RAYS_VARIANT_NONE};
     DevBuf inode, wnode, ibox, leaf, tnorm, objids, mats, lights, jitter;
     DevBuf fnode;    // 2^f_log2-ary records of the frustum traversal (empty: it takes wnode's 4-ary ones)
     DevBuf qent, qhdr;  // fnode quantised (build_quant_records): the big-scene kernels' records
@@ -1774,6 +1776,180 @@ extern "C" int rt_shade_rays(rt_scene* s, const rt_ray* rays, const uint32_t* se
 
 extern "C" int rt_shade_rays_variant(const rt_scene* s) {
     return s ? s->shade_variant.load(std::memory_order_relaxed) : RT_RAYS_VARIANT_NONE;
+}
+
+// ---- hit records (rt_query.hpp, trace_hits_kernel) ---------------------------------------------
+static_assert(sizeof(rt_hit) == 64 && sizeof(HitWords) == sizeof(rt_hit), "rt_hit is four 16-byte words");
+
+namespace {
+// As trace_rays_args: no HIP call and no read through s before the checks pass.
+int trace_hits_args(const rt_scene* s, const void* rays, size_t n, int flags, const rt_hit* hits) {
+    if (!s) return set_error(RT_ERR_ARG, "rt_trace_hits: null scene");
+    if (flags & ~RT_FLAG_BINARY) return set_error(RT_ERR_ARG, "rt_trace_hits: unknown flag");
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_trace_hits: more than 2^31-1 rays in one batch");
+    if (!rays || !hits) return set_error(RT_ERR_ARG, "rt_trace_hits: null rays or hits");
+    return RT_OK;
+}
+
+// One launch on st under trace_rays_launch's variant rule; of the scene it writes hits_variant alone.
+int trace_hits_launch(rt_scene* s, const rt_ray* rays, size_t n, int flags, rt_hit* hits, hipStream_t st) {
+    int variant = RT_RAYS_VARIANT_DEEP;
+    if (!s->deep) {
+        if (s->wide && s->lane_wide && !(flags & RT_FLAG_BINARY)) variant = RT_RAYS_VARIANT_WIDE;
+        else if (s->lane_stack) variant = RT_RAYS_VARIANT_BINARY;
+    }
+    if (s->deep && !s->tri.p) return set_error(RT_ERR_INTERNAL, "rt_trace_hits: a deep scene without its triangle array");
+    HitsParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.sc = scene_view(s);  // (the packed records, tnorm, objids and the material table's bounds)
+    Q.sc.wide = variant == RT_RAYS_VARIANT_WIDE ? 1 : 0;
+    Q.sc.f_log2 = 2;
+    Q.sc.ncut = 0;
+    Q.rays = reinterpret_cast<const float*>(rays);
+    Q.n = uint32_t(n);
+    Q.hits = reinterpret_cast<uint4*>(hits);
+    const dim3 grid((Q.n + BLOCK - 1) / BLOCK), block(BLOCK);
+    if (variant == RT_RAYS_VARIANT_WIDE) hipLaunchKernelGGL((trace_hits_kernel<RT_RAYS_VARIANT_WIDE>), grid, block, 0, st, Q);
+    else if (variant == RT_RAYS_VARIANT_BINARY) hipLaunchKernelGGL((trace_hits_kernel<RT_RAYS_VARIANT_BINARY>), grid, block, 0, st, Q);
+    else hipLaunchKernelGGL((trace_hits_kernel<RT_RAYS_VARIANT_DEEP>), grid, block, 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    s->hits_variant.store(variant, std::memory_order_relaxed);
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_trace_hits_device(rt_scene* s, const rt_ray* rays, size_t n, int flags, rt_hit* hits, void* stream) {
+    const int rc = trace_hits_args(s, rays, n, flags, hits);
+    if (rc != RT_OK) return rc;
+    // the kernel stores 16-byte words
+    if (reinterpret_cast<uintptr_t>(hits) % 16 != 0) return set_error(RT_ERR_ARG, "rt_trace_hits_device: hits_dev is not 16-byte aligned");
+    if (n == 0) return RT_OK;
+    DeviceGuard g(s->device);
+    return trace_hits_launch(s, rays, n, flags, hits, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rt_trace_hits(rt_scene* s, const rt_ray* rays, size_t n, int flags, rt_hit* hits, float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.0f;
+    int rc = trace_hits_args(s, rays, n, flags, hits);
+    if (rc != RT_OK || n == 0) return rc;
+    DeviceGuard g(s->device);
+    DevBuf dr, dh;
+    if ((rc = dr.upload(rays, n * sizeof(rt_ray))) != RT_OK) return rc;
+    if ((rc = dh.alloc(n * sizeof(rt_hit))) != RT_OK) return rc;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } ev;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, nullptr));
+    }
+    rc = trace_hits_launch(s, static_cast<const rt_ray*>(dr.p), n, flags, static_cast<rt_hit*>(dh.p), nullptr);
+    if (rc != RT_OK) return rc;
+    if (kernel_ms) HIP_TRY(hipEventRecord(ev.b, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    HIP_TRY(hipMemcpy(hits, dh.p, n * sizeof(rt_hit), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_trace_hits_variant(const rt_scene* s) {
+    return s ? s->hits_variant.load(std::memory_order_relaxed) : RT_RAYS_VARIANT_NONE;
+}
+
+// The host build of the record: intersectTriangle(ray_i, tris[i], 1e-4f, FLT_MAX) through mt_g and
+// hit_record, the functions trace_hits_kernel runs.
+extern "C" int rt_hit_record_host(const rt_ray* rays, const rt_triangle* tris, int n, rt_hit* out) {
+    if (n < 0 || (n > 0 && (!rays || !tris || !out))) return set_error(RT_ERR_ARG, "rt_hit_record_host: bad args");
+    for (int i = 0; i < n; ++i) {
+        const rt_ray& q = rays[i];
+        const rt_triangle& T = tris[i];
+        const RayPre r = make_ray_mt(mk(q.origin.x, q.origin.y, q.origin.z), mk(q.direction.x, q.direction.y, q.direction.z));
+        const f3 v0 = mk(T.v0.x, T.v0.y, T.v0.z);
+        const f3 e1 = sub(mk(T.v1.x, T.v1.y, T.v1.z), v0), e2 = sub(mk(T.v2.x, T.v2.y, T.v2.z), v0);
+        float t = 0.f, u = 0.f, v = 0.f;
+        HitWords h = miss_record();
+        if (mt_g(r, v0, e1, e2, kRayTMin, FLT_MAX, t, u, v))
+            h = hit_record(r, e1, e2, mk(T.n0.x, T.n0.y, T.n0.z), mk(T.n1.x, T.n1.y, T.n1.z), mk(T.n2.x, T.n2.y, T.n2.z), t, u,
+                           v, i, -1, -1);
+        std::memcpy(&out[i], &h, sizeof(rt_hit));
+    }
+    return RT_OK;
+}
+
+// ---- camera rays (rt_query.hpp, camera_rays_kernel) --------------------------------------------
+namespace {
+// The checks of rt_camera_rays_host / _device: no HIP call before they pass.  *n_out: W * rows * spp.
+int camera_rays_args(const rt_camera* cam, int spp, int row0, int rows, const void* rays, size_t* n_out) {
+    if (!cam || !rays) return set_error(RT_ERR_ARG, "rt_camera_rays: null camera or rays");
+    if (spp < 1) return set_error(RT_ERR_ARG, "rt_camera_rays: spp < 1");
+    const int W = cam->pixel_width, H = cam->pixel_height;
+    if (W < 1 || H < 1) return set_error(RT_ERR_ARG, "rt_camera_rays: an empty image");
+    if (row0 < 0 || rows < 0 || row0 > H || rows > H - row0) return set_error(RT_ERR_ARG, "rt_camera_rays: rows outside the image");
+    const unsigned long long n = (unsigned long long)W * (unsigned long long)rows * (unsigned long long)spp;
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_camera_rays: more than 2^31-1 rays in one call");
+    *n_out = size_t(n);
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_camera_rays_host(const rt_camera* cam, int spp, const float* jitter, int row0, int rows, rt_ray* rays,
+                                   uint32_t* seeds) {
+    size_t n = 0;
+    int rc = camera_rays_args(cam, spp, row0, rows, rays, &n);
+    if (rc != RT_OK || n == 0) return rc;
+    std::vector<float> tab;
+    if (!jitter) {
+        tab.resize(size_t(2) * size_t(spp));
+        if ((rc = rt_jittered_samples(spp, 42u, 1, tab.data())) != RT_OK) return rc;
+        jitter = tab.data();
+    }
+    const f3 center = mk(cam->center.x, cam->center.y, cam->center.z);
+    const f3 p00 = mk(cam->pixel00_loc.x, cam->pixel00_loc.y, cam->pixel00_loc.z);
+    const f3 du = mk(cam->pixel_delta_u.x, cam->pixel_delta_u.y, cam->pixel_delta_u.z);
+    const f3 dv = mk(cam->pixel_delta_v.x, cam->pixel_delta_v.y, cam->pixel_delta_v.z);
+    const int W = cam->pixel_width;
+    size_t i = 0;
+    for (int y = row0; y < row0 + rows; ++y)
+        for (int x = 0; x < W; ++x)
+            for (int s = 0; s < spp; ++s, ++i) {
+                const f3 d = camera_dir(center, p00, du, dv, x, y, jitter[2 * s], jitter[2 * s + 1]);
+                rays[i].origin = cam->center;
+                rays[i].direction = rt_vec3{d.x, d.y, d.z};
+                if (seeds) seeds[i] = make_rng_seed(x, y, s);
+            }
+    return RT_OK;
+}
+
+extern "C" int rt_camera_rays_device(int device, const rt_camera* cam, int spp, const float* jitter, int row0, int rows,
+                                     rt_ray* rays, uint32_t* seeds, void* stream) {
+    size_t n = 0;
+    int rc = camera_rays_args(cam, spp, row0, rows, rays, &n);
+    if (rc != RT_OK) return rc;
+    if (!jitter) return set_error(RT_ERR_ARG, "rt_camera_rays_device: null jitter table");
+    if (n == 0) return RT_OK;
+    if ((rc = check_device(device)) != RT_OK) return rc;
+    DeviceGuard g(device);
+    CameraRaysParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.center = mk(cam->center.x, cam->center.y, cam->center.z);
+    P.p00 = mk(cam->pixel00_loc.x, cam->pixel00_loc.y, cam->pixel00_loc.z);
+    P.du = mk(cam->pixel_delta_u.x, cam->pixel_delta_u.y, cam->pixel_delta_u.z);
+    P.dv = mk(cam->pixel_delta_v.x, cam->pixel_delta_v.y, cam->pixel_delta_v.z);
+    P.W = cam->pixel_width;
+    P.spp = spp;
+    P.row0 = row0;
+    P.n = uint32_t(n);
+    P.jitter = jitter;
+    P.rays = reinterpret_cast<float*>(rays);
+    P.seeds = seeds;
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((P.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 void rt::scene_set_caller_ordered(rt_scene* s, bool on) {

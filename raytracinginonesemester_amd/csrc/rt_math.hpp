@@ -339,6 +339,44 @@ __host__ __device__ __forceinline__ void hit_frame(const RayPre& r, f3 e1, f3 e2
     shadingN = sN;
 }
 
+// The same completion with everything intersectTriangle derives on the way kept (the hit records
+// of rt_trace_hits): geomN after its flip towards the ray (query.h:115-117) and rec.front_face.
+// A sibling, not a wrapper: hit_frame's callers keep their own code.
+struct HitFrame {
+    f3 p, shadingN, geomN;
+    bool front;
+};
+__host__ __device__ __forceinline__ HitFrame hit_frame_full(const RayPre& r, f3 e1, f3 e2, f3 n0, f3 n1, f3 n2, float t,
+                                                            float u, float v) {
+    HitFrame h;
+    h.p = add(r.o, scale(r.d, t));
+    f3 geomN = unit(cross(e1, e2));
+    h.front = dot(r.d, geomN) < 0.0f;
+    if (!h.front) geomN = neg(geomN);
+    const float w = 1.0f - u - v;
+    f3 sN = add(add(scale(n0, w), scale(n1, u)), scale(n2, v));
+    if (dot(sN, sN) < 1e-12f) {
+        sN = geomN;
+    } else {
+        sN = unit(sN);
+        if (dot(sN, geomN) < 0.0f) sN = neg(sN);
+    }
+    h.shadingN = sN;
+    h.geomN = geomN;
+    return h;
+}
+
+// Camera::get_ray(float, float) (camera.h:49-53): the direction of sample (x + jx, y + jy),
+// unit_vector(pix - center) with pix = (p00 + du*px) + dv*py and Camera::unit_vector's double
+// division and fallback (camera.h:218-223).  The expression of the render kernels' camera_ray
+// (rt_shade.hpp), which keeps its own text: written through this helper, 27 render kernels came
+// out with other instruction schedules (scripts/isa_diff.py), and those kernels are pinned.
+__host__ __device__ __forceinline__ f3 camera_dir(f3 center, f3 p00, f3 du, f3 dv, int x, int y, float jx, float jy) {
+    const float px = (float)x + jx, py = (float)y + jy;
+    const f3 pix = add(add(p00, scale(du, px)), scale(dv, py));
+    return cam_unit(sub(pix, center));
+}
+
 // G/include/query.h:32-48
 __host__ __device__ __forceinline__ float rng_next(uint32_t& state) {
     state = state * 1664525u + 1013904223u;

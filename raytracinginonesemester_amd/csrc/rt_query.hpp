@@ -3,6 +3,8 @@
 // of IsInShadow (G/include/shader.h:59-61).  One ray per lane over the per-lane traversals of
 // rt_traverse.hpp; DESIGN.md §4.17.  Below them the radiance queries (rt_shade_rays*):
 // TraceRayIterative (G/include/query.h:156-220) for caller rays, one path per lane; §4.18.
+// Then the hit records (rt_trace_hits*): the closest hit as the reference's whole HitRecord, and
+// the camera rays that feed any of the three (rt_camera_rays*); §4.19.
 // Part of rt_device.hip's translation unit, included inside its anonymous namespace after rt_shade.hpp.
 #pragma once
 
@@ -166,4 +168,114 @@ __global__ __launch_bounds__(BLOCK) void shade_rays_kernel(ShadeParams S) {
     S.radiance[3 * (size_t)i] = c.x;
     S.radiance[3 * (size_t)i + 1] = c.y;
     S.radiance[3 * (size_t)i + 2] = c.z;
+}
+
+// ---- hit records (rt_trace_hits*): SearchBVH's HitRecord for caller rays, DESIGN.md §4.19 ----
+// rt_hit (include/rt_mi355x.h) as the four 16-byte words it is stored in.
+struct HitWords {
+    uint4 w[4];
+};
+// A miss: tri -1, t -1.0f, every other field zero.
+__host__ __device__ __forceinline__ HitWords miss_record() {
+    HitWords h;
+    h.w[0] = make_uint4(0xFFFFFFFFu, pw::asu(-1.0f), 0u, 0u);
+    h.w[1] = h.w[2] = h.w[3] = make_uint4(0u, 0u, 0u, 0u);
+    return h;
+}
+// intersectTriangle's record (query.h:110-128) of a triangle the ray is known to hit at (t, u, v),
+// with the ids assignMaterialToHit reads.
+__host__ __device__ __forceinline__ HitWords hit_record(const RayPre& r, f3 e1, f3 e2, f3 n0, f3 n1, f3 n2, float t, float u,
+                                                        float v, int32_t tri, int32_t object_id, int32_t material) {
+    const HitFrame f = hit_frame_full(r, e1, e2, n0, n1, n2, t, u, v);
+    HitWords h;
+    h.w[0] = make_uint4((uint32_t)tri, pw::asu(t), pw::asu(u), pw::asu(v));
+    h.w[1] = make_uint4(pw::asu(f.p.x), pw::asu(f.p.y), pw::asu(f.p.z), pw::asu(f.shadingN.x));
+    h.w[2] = make_uint4(pw::asu(f.shadingN.y), pw::asu(f.shadingN.z), pw::asu(f.geomN.x), pw::asu(f.geomN.y));
+    h.w[3] = make_uint4(pw::asu(f.geomN.z), f.front ? 1u : 0u, (uint32_t)object_id, (uint32_t)material);
+    return h;
+}
+
+struct HitsParams {
+    SceneView sc;
+    const float* __restrict__ rays;  // n x rt_ray
+    uint32_t n;
+    uint4* __restrict__ hits;  // n x rt_hit, 16-byte aligned
+};
+
+// trace_rays_kernel's closest-hit traversal, then the winner's whole record in the same lane: the
+// traversal leaves a slot of the packed leaf array (or, DEEP, BRUTE_BIT | triangle), and the
+// record is rebuilt from that leaf and the ray as resolve_hit rebuilds it -- the accepting test's
+// own t, u, v.  objids / mats: the range tests of material_of, which selects by them.  A lane
+// stores its 64 bytes as four 16-byte words, so a wave writes 4 KiB contiguous.
+template <int VARIANT>
+__global__ __launch_bounds__(BLOCK) void trace_hits_kernel(HitsParams Q) {
+    constexpr bool LDS = VARIANT != RT_RAYS_VARIANT_DEEP;
+    constexpr bool DEEP = !LDS;
+    __shared__ uint32_t stk[LDS ? LANE_LDS_CAP * BLOCK : 1];
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;  // n < 2^31
+    if (i >= Q.n) return;
+    const SceneView& sc = Q.sc;
+    const float* R = Q.rays + 6 * (size_t)i;
+    const RayPre r = make_ray(mk(R[0], R[1], R[2]), mk(R[3], R[4], R[5]), scene_bmax(sc));
+    HitState hs;
+    shade_traverse<VARIANT>(sc, r, false, 0.0f, hs, stk + (LDS ? threadIdx.x : 0));
+    HitWords h = miss_record();
+    if (hs.slot >= 0) {
+        const int32_t slot = hs.slot;
+        const float4* L = sc.leaf + 4 * (size_t)slot;
+        bool brute = false;
+        if constexpr (DEEP) {
+            brute = ((uint32_t)slot & BRUTE_BIT) != 0;
+            if (brute) L = sc.tri + 3 * (size_t)((uint32_t)slot & ~BRUTE_BIT);
+        }
+        const float4 a = L[0], b = L[1], c = L[2];
+        const f3 v0 = mk(a.x, a.y, a.z), e1 = mk(b.x, b.y, b.z), e2 = mk(b.w, c.x, c.y);
+        float t = 0.f, u = 0.f, v = 0.f;
+        mt_g(r, v0, e1, e2, -FLT_MAX, FLT_MAX, t, u, v);  // same t/u/v as the accepting test
+        const int32_t tri = brute ? (int32_t)((uint32_t)slot & ~BRUTE_BIT) : __float_as_int(a.w);
+        const float4* Nn = sc.tnorm + 3 * (size_t)tri;
+        const float4 n0 = Nn[0], n1 = Nn[1], n2 = Nn[2];
+        int32_t oid = -1, mat = -1;
+        if (sc.objids != nullptr && tri >= 0 && tri < sc.num_tris) {
+            oid = sc.objids[tri];
+            if (sc.mats != nullptr && oid >= 0 && oid < sc.num_mats) mat = oid;
+        }
+        h = hit_record(r, e1, e2, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z), mk(n2.x, n2.y, n2.z), t, u, v, tri, oid, mat);
+    }
+    uint4* out = Q.hits + 4 * (size_t)i;
+    out[0] = h.w[0];
+    out[1] = h.w[1];
+    out[2] = h.w[2];
+    out[3] = h.w[3];
+}
+
+// ---- camera rays on the device (rt_camera_rays_device), DESIGN.md §4.19 -----------------------
+struct CameraRaysParams {
+    f3 center, p00, du, dv;
+    int32_t W, spp, row0;
+    uint32_t n;  // W * rows * spp < 2^31
+    const float* __restrict__ jitter;  // 2 * spp
+    float* __restrict__ rays;          // n x rt_ray
+    uint32_t* __restrict__ seeds;      // n, or null
+};
+
+// One sample per lane in the order of the reference's AOVs, ((y - row0) W + x) spp + s, so
+// consecutive lanes write consecutive rays: the rays render() shoots (camera_dir, the arithmetic
+// of the render kernels' camera_ray) and the rng states it seeds them with (query.cu:146-158).
+__global__ __launch_bounds__(BLOCK) void camera_rays_kernel(CameraRaysParams P) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= P.n) return;
+    const uint32_t pix = i / (uint32_t)P.spp;
+    const int s = (int)(i - pix * (uint32_t)P.spp);
+    const uint32_t yl = pix / (uint32_t)P.W;
+    const int x = (int)(pix - yl * (uint32_t)P.W), y = P.row0 + (int)yl;
+    const f3 d = camera_dir(P.center, P.p00, P.du, P.dv, x, y, P.jitter[2 * s], P.jitter[2 * s + 1]);
+    float* R = P.rays + 6 * (size_t)i;
+    R[0] = P.center.x;
+    R[1] = P.center.y;
+    R[2] = P.center.z;
+    R[3] = d.x;
+    R[4] = d.y;
+    R[5] = d.z;
+    if (P.seeds != nullptr) P.seeds[i] = make_rng_seed(x, y, s);
 }
