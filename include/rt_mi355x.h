@@ -32,7 +32,11 @@ extern "C" {
                                  existing changed): rt_shade_opts, rt_shade_opts_default,
                                  rt_shade_rays, rt_shade_rays_device, rt_shade_rays_variant; rt_hit,
                                  rt_trace_hits, rt_trace_hits_device, rt_trace_hits_variant,
-                                 rt_hit_record_host, rt_camera_rays_host, rt_camera_rays_device */
+                                 rt_hit_record_host, rt_camera_rays_host, rt_camera_rays_device; rt_film,
+                                 rt_film_create, rt_film_destroy, rt_film_clear_device,
+                                 rt_film_add_device, rt_film_resolve_device, rt_film_row_samples,
+                                 rt_film_pixels_host, rt_camera_rays_pass_host,
+                                 rt_camera_rays_pass_device */
 
 enum {
     RT_OK = 0,
@@ -606,6 +610,56 @@ int rt_camera_rays_host(const rt_camera* cam, int spp, const float* jitter, int 
                         uint32_t* seeds);
 int rt_camera_rays_device(int device, const rt_camera* cam, int spp, const float* jitter_dev, int row0, int rows,
                           rt_ray* rays_dev, uint32_t* seeds_dev, void* hip_stream);
+/* The same for samples [sample0, sample0 + nsamples) of a longer table (a frame made in sample
+ * passes): jitter holds the 2*nsamples floats of that slice, ray ((y - row0) * W + x) * nsamples + s
+ * is sample sample0 + s of pixel (x, y) and its seed is make_rng_seed(x, y, sample0 + s).
+ * sample0 == 0 is the call above; sample0 < 0 (or sample0 + nsamples past 2^31-1) is RT_ERR_ARG, and
+ * so is a null jitter with sample0 > 0 on the host (the default table is a whole frame's). */
+int rt_camera_rays_pass_host(const rt_camera* cam, int sample0, int nsamples, const float* jitter, int row0, int rows,
+                             rt_ray* rays, uint32_t* seeds);
+int rt_camera_rays_pass_device(int device, const rt_camera* cam, int sample0, int nsamples, const float* jitter_dev,
+                               int row0, int rows, rt_ray* rays_dev, uint32_t* seeds_dev, void* hip_stream);
+
+/* ---- film: radiance samples to a frame, on the device ---------------------------------------
+ * The last step of a frame made from caller rays: per pixel and channel the
+ * float sum of the radiance samples in the order they are added, col = col + sample as render()
+ * adds them (G/include/query.cu:130-166), and from it render()'s pixel
+ * float(double(col) / double(float(count))) and write_p6's byte.  camera rays -> rt_shade_rays ->
+ * film is rt_render's frame bit for bit, and so is a film fed samples 0..k-1, then k..N-1, in row
+ * bands or whole: the float sum is the same sequence of adds.
+ * A film holds W*H*3 float sums on its device and a sample count per row on the host, updated when
+ * a call is enqueued.  It takes no scene and touches no frame ordering, event or buffer of
+ * rt_render_device.  Every call is one launch on the caller's hip_stream (NULL = the null stream),
+ * asynchronous and ordered with the other film calls of that stream; calls on one film from
+ * different streams or threads are the caller's to order.  Every argument check runs before any
+ * HIP call.  Results are specified for finite radiance.
+ * RT_ERR_ARG: a null film or radiance, nsamples < 1, rows outside the image, a resolve with both
+ * outputs null or over rows whose counts differ or are 0.  rows * W * nsamples > 2^31-1 is
+ * RT_ERR_UNSUPPORTED; rows == 0 is RT_OK with no launch.
+ * (Additive to ABI 3: rt_film, rt_film_create, rt_film_destroy, rt_film_clear_device,
+ * rt_film_add_device, rt_film_resolve_device, rt_film_row_samples, rt_film_pixels_host,
+ * rt_camera_rays_pass_host, rt_camera_rays_pass_device.) */
+typedef struct rt_film rt_film;
+/* Sums of a width x height image on `device`, zeroed (synchronous). */
+int rt_film_create(int device, int width, int height, rt_film** out);
+void rt_film_destroy(rt_film* f);
+/* The sums and every row's count to 0. */
+int rt_film_clear_device(rt_film* f, void* hip_stream);
+/* radiance_dev: rows*W*nsamples*3 floats, sample s of pixel (x, y) at ((y - row0) * W + x) * nsamples + s:
+ * the order of rt_camera_rays_* and of rt_shade_rays' output for those rays.  Any alignment; a
+ * 16-byte aligned pointer takes the faster kernel. */
+int rt_film_add_device(rt_film* f, const float* radiance_dev, int row0, int rows, int nsamples, void* hip_stream);
+/* rgb_dev (rows*W*3 floats) and/or p6_dev (rows*W*3 bytes, write_p6's defaults as
+ * rt_render_device_p6 writes them); one of them may be NULL.  Does not clear: a film can be resolved
+ * after every pass. */
+int rt_film_resolve_device(rt_film* f, int row0, int rows, float* rgb_dev, uint8_t* p6_dev, void* hip_stream);
+/* Samples added to that row since the film was made or cleared. */
+int rt_film_row_samples(const rt_film* f, int row, int64_t* count);
+/* Host build of the film's arithmetic (no device needed): adds radiance (rows*width*nsamples*3
+ * floats, the layout above) to sum_inout (rows*width*3 running sums) and, unless rgb_out is NULL,
+ * writes the pixels of count_after samples per pixel, the count after this add (>= nsamples). */
+int rt_film_pixels_host(const float* radiance, int width, int rows, int nsamples, float* sum_inout,
+                        int64_t count_after, float* rgb_out);
 
 /* The Blinn-Phong powf of the kernels (restatement of the reference libm's powf, see
  * csrc/rt_math.hpp): rt_powf_host evaluates the host build, rt_powf_batch the device build

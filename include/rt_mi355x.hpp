@@ -175,6 +175,65 @@ inline std::vector<rt_ray> camera_rays(const Camera& cam, int spp, int row0, int
     return rays;
 }
 
+// One sample pass of a longer frame (rt_camera_rays_pass_host): samples [sample0, sample0 + jitter.size() / 2)
+// with their slice of the frame's jitter table (jx, jy per sample); seeds make_rng_seed(x, y, sample0 + s).
+inline std::vector<rt_ray> camera_rays_pass(const Camera& cam, int sample0, const std::vector<float>& jitter, int row0,
+                                            int rows, std::vector<uint32_t>* seeds = nullptr) {
+    const int ns = int(jitter.size() / 2);
+    if (ns < 1 || jitter.size() % 2 != 0 || rows < 0) throw Error(RT_ERR_ARG, "camera_rays_pass: an empty or odd jitter table or rows < 0");
+    const size_t n = size_t(cam.width()) * size_t(rows) * size_t(ns);
+    std::vector<rt_ray> rays(n ? n : 1);
+    if (seeds) seeds->assign(n ? n : 1, 0u);
+    check(rt_camera_rays_pass_host(&cam.c, sample0, ns, jitter.data(), row0, rows, rays.data(), seeds ? seeds->data() : nullptr));
+    rays.resize(n);
+    if (seeds) seeds->resize(n);
+    return rays;
+}
+
+// Per-pixel sums of radiance samples on a device (rt_film): add samples in render()'s order, resolve to
+// render()'s float pixels and P6 bytes.  Device pointers; every call is one launch on hip_stream.
+class Film {
+public:
+    Film(int width, int height, int device = 0) : w_(width), h_(height) { check(rt_film_create(device, width, height, &f_)); }
+    Film(const Film&) = delete;
+    Film& operator=(const Film&) = delete;
+    ~Film() { if (f_) rt_film_destroy(f_); }
+    rt_film* get() const { return f_; }
+    int width() const { return w_; }
+    int height() const { return h_; }
+    // radiance_dev: rows*W*nsamples*3 floats, sample s of pixel (x, y) at ((y - row0) * W + x) * nsamples + s
+    void add(const float* radiance_dev, int row0, int rows, int nsamples, void* hip_stream = nullptr) {
+        check(rt_film_add_device(f_, radiance_dev, row0, rows, nsamples, hip_stream));
+    }
+    // rgb_dev: rows*W*3 floats, p6_dev: rows*W*3 bytes; one of them may be null.  Does not clear.
+    void resolve(int row0, int rows, float* rgb_dev, uint8_t* p6_dev, void* hip_stream = nullptr) {
+        check(rt_film_resolve_device(f_, row0, rows, rgb_dev, p6_dev, hip_stream));
+    }
+    void clear(void* hip_stream = nullptr) { check(rt_film_clear_device(f_, hip_stream)); }
+    int64_t row_samples(int row) const {
+        int64_t n = 0;
+        check(rt_film_row_samples(f_, row, &n));
+        return n;
+    }
+
+private:
+    rt_film* f_ = nullptr;
+    int w_ = 0, h_ = 0;
+};
+
+// The film's arithmetic on the host (rt_film_pixels_host): adds radiance (rows*width*nsamples*3) to sums
+// (rows*width*3, resized and zeroed when empty) and returns the pixels of count_after samples per pixel.
+inline std::vector<float> film_pixels_host(const std::vector<float>& radiance, int width, int rows, int nsamples,
+                                           std::vector<float>& sums, int64_t count_after) {
+    const size_t px = size_t(width > 0 ? width : 0) * size_t(rows > 0 ? rows : 0) * 3;
+    if (sums.empty()) sums.assign(px, 0.0f);
+    if (sums.size() != px || nsamples < 1 || radiance.size() != px * size_t(nsamples))
+        throw Error(RT_ERR_ARG, "film_pixels_host: radiance and sums do not match the shape");
+    std::vector<float> rgb(px);
+    if (px) check(rt_film_pixels_host(radiance.data(), width, rows, nsamples, sums.data(), count_after, rgb.data()));
+    return rgb;
+}
+
 inline void write_p6(const std::string& path, const Framebuffer& fb, const rt_ppm_options* opt = nullptr) {
     check(rt_ppm_write(path.c_str(), fb.rgb.data(), fb.width, fb.height, opt));
 }

@@ -211,6 +211,15 @@ SIGNATURES = {
     "rt_hit_record_host": (I, [P, P, I, P]),
     "rt_camera_rays_host": (I, [P, I, P, I, I, P, P]),
     "rt_camera_rays_device": (I, [I, P, I, P, I, I, P, P, P]),
+    "rt_camera_rays_pass_host": (I, [P, I, I, P, I, I, P, P]),
+    "rt_camera_rays_pass_device": (I, [I, P, I, I, P, I, I, P, P, P]),
+    "rt_film_create": (I, [I, I, I, P]),
+    "rt_film_destroy": (None, [P]),
+    "rt_film_clear_device": (I, [P, P]),
+    "rt_film_add_device": (I, [P, P, I, I, I, P]),
+    "rt_film_resolve_device": (I, [P, I, I, P, P, P]),
+    "rt_film_row_samples": (I, [P, I, P]),
+    "rt_film_pixels_host": (I, [P, I, I, I, P, C.c_int64, P]),
     "rt_powf_host": (C.c_float, [C.c_float, C.c_float]),
     "rt_debug_frustum_records": (C.c_int, [C.c_size_t, P, P, C.c_int, C.c_int, P, P, C.c_size_t]),
     "rt_debug_scene_pack": (I, [SZ, P, P, P, P, P]),

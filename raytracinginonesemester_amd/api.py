@@ -477,6 +477,51 @@ class DeviceScene:
         """The traversal the latest shade_rays call launched (RT_RAYS_VARIANT_*)."""
         return int(lib().rt_shade_rays_variant(self._handle()))
 
+    def render_rays(self, camera: Camera, spp: int, max_depth: int = 1, diffuse_bounce: bool = True,
+                    miss_color=(0, 0, 0), jitter=None, pass_spp: Optional[int] = None,
+                    band_rows: Optional[int] = None, ray_fn=None, p6: bool = False, film: Optional["Film"] = None):
+        """A frame through the query path, on the device: for every sample pass (``pass_spp``
+        samples; default all) and row band (``band_rows`` rows; default all) camera_rays ->
+        ``ray_fn`` -> shade_rays -> Film.add, then one Film.resolve.  Memory is bounded by one
+        band of one pass; with ``ray_fn=None`` the frame is render()'s bit for bit.
+
+        ``ray_fn(rays, seeds, row0, rows, sample0, n) -> rays`` is the hook of a camera of one's
+        own (thin lens, fisheye, resampling): it gets the pinhole rays ((rows*W*n, 6) float32 tensor)
+        and seeds of the step and returns the rays to shade, same shape and order.
+        ``jitter``: (spp, 2) float32, None for jittered_samples(spp).  ``film``: a Film of the
+        camera's size to accumulate into (neither cleared before nor closed after: samples already
+        there stay in the sums); default a new one, closed on return.
+        Returns Film.resolve's result for the whole image, on torch's current stream."""
+        W, H, spp = camera.pixel_width, camera.pixel_height, int(spp)
+        if spp < 1:
+            raise ValueError("render_rays: spp < 1")
+        pass_spp = spp if pass_spp is None else int(pass_spp)
+        band_rows = H if band_rows is None else int(band_rows)
+        if pass_spp < 1 or band_rows < 1:
+            raise ValueError("render_rays: pass_spp and band_rows must be positive")
+        jit = (jittered_samples(spp) if jitter is None else _c(jitter, np.float32)).reshape(-1, 2)
+        if jit.shape[0] != spp:
+            raise ValueError("render_rays: jitter must hold (spp, 2) floats")
+        own = film is None
+        if own:
+            film = Film(W, H, self.device)
+        elif (film.width, film.height, film.device) != (W, H, self.device):
+            raise ValueError("render_rays: the film is not of the camera's size on the scene's device")
+        try:
+            for s0 in range(0, spp, pass_spp):
+                n = min(pass_spp, spp - s0)
+                for r0 in range(0, H, band_rows):
+                    rows = min(band_rows, H - r0)
+                    rays, seeds = camera_rays(camera, n, jit[s0:s0 + n], r0, rows, device=self.device, sample0=s0)
+                    if ray_fn is not None:
+                        rays = ray_fn(rays, seeds, r0, rows, s0, n)
+                    rad = self.shade_rays(rays, seeds, max_depth, diffuse_bounce, miss_color)
+                    film.add(rad, r0, rows, n)
+            return film.resolve(p6=p6)
+        finally:
+            if own:
+                film.close()
+
     def trace_hits(self, rays, flags: int = 0, stream: Optional[int] = None, timing: bool = False):
         """Hit records of caller rays (rt_trace_hits / rt_trace_hits_device): per ray the HitRecord
         SearchBVH returns (G/include/query.h:224-311, intersectTriangle's tail :110-130) with the ids
@@ -820,7 +865,7 @@ def hit_fields(hits) -> dict:
 
 
 def camera_rays(camera: Camera, spp: int = 1, jitter=None, row0: int = 0, rows: Optional[int] = None,
-                device: Optional[int] = None, stream: Optional[int] = None):
+                device: Optional[int] = None, stream: Optional[int] = None, sample0: int = 0):
     """The camera rays of image rows [row0, row0 + rows) (default: to the last row) and their rng
     seeds, as render() makes them (rt_camera_rays_host / rt_camera_rays_device): ray
     ((y - row0) * W + x) * spp + s is sample s of pixel (x, y), Camera::get_ray of
@@ -830,8 +875,14 @@ def camera_rays(camera: Camera, spp: int = 1, jitter=None, row0: int = 0, rows: 
     ``device=None``: the host build, numpy ``(rays (n, 6) float32, seeds (n,) uint32)``.  An int
     device: one launch on ``stream`` of that device (a HIP stream handle; default torch's current
     stream), torch tensors ``(rays (n, 6) float32, seeds (n,) int32)``, the seeds' 32 bits as
-    DeviceScene.shade_rays takes them; nothing passes through the host but the jitter table."""
-    spp = int(spp)
+    DeviceScene.shade_rays takes them; nothing passes through the host but the jitter table.
+
+    ``sample0`` > 0: one sample pass of a longer frame (rt_camera_rays_pass_*): the ``spp`` samples
+    are samples [sample0, sample0 + spp) of the frame's, ``jitter`` is that slice of the frame's
+    table (required) and the seeds are make_rng_seed(x, y, sample0 + s)."""
+    spp, sample0 = int(spp), int(sample0)
+    if sample0 != 0 and jitter is None:
+        raise ValueError("camera_rays: a pass with sample0 != 0 needs its slice of the jitter table")
     H = camera.pixel_height
     if rows is None:
         rows = H - int(row0)
@@ -844,7 +895,11 @@ def camera_rays(camera: Camera, spp: int = 1, jitter=None, row0: int = 0, rows: 
     if device is None:
         rays = np.zeros((n, 6), np.float32)
         seeds = np.zeros(n, np.uint32)
-        check(lib().rt_camera_rays_host(C.byref(camera.c), spp, ptr(jit), int(row0), int(rows), ptr(rays), ptr(seeds)))
+        if sample0 != 0:
+            check(lib().rt_camera_rays_pass_host(C.byref(camera.c), sample0, spp, ptr(jit), int(row0), int(rows), ptr(rays),
+                                                 ptr(seeds)))
+        else:
+            check(lib().rt_camera_rays_host(C.byref(camera.c), spp, ptr(jit), int(row0), int(rows), ptr(rays), ptr(seeds)))
         return rays, seeds
     import torch
 
@@ -859,11 +914,131 @@ def camera_rays(camera: Camera, spp: int = 1, jitter=None, row0: int = 0, rows: 
     foreign = stream is not None and stream != cur.cuda_stream
     if foreign:  # the table must be there before the launch is queued on the caller's stream
         cur.synchronize()
-    check(lib().rt_camera_rays_device(int(device), C.byref(camera.c), spp, jd.data_ptr(), int(row0), int(rows),
-                                      rays.data_ptr(), seeds.data_ptr(), stream if foreign else cur.cuda_stream))
+    st = stream if foreign else cur.cuda_stream
+    if sample0 != 0:
+        check(lib().rt_camera_rays_pass_device(int(device), C.byref(camera.c), sample0, spp, jd.data_ptr(), int(row0),
+                                               int(rows), rays.data_ptr(), seeds.data_ptr(), st))
+    else:
+        check(lib().rt_camera_rays_device(int(device), C.byref(camera.c), spp, jd.data_ptr(), int(row0), int(rows),
+                                          rays.data_ptr(), seeds.data_ptr(), st))
     if foreign:  # ... and stay until that launch has read it
         jd.record_stream(torch.cuda.ExternalStream(stream, device=dev))
     return rays, seeds
+
+
+class Film:
+    """Per-pixel float sums of radiance samples on one device (rt_film): the last step of a frame
+    made from caller rays.  ``add`` adds samples in order as render() does (col = col + sample),
+    ``resolve`` gives render()'s pixels float(double(col) / double(float(count))) and write_p6's
+    bytes; camera_rays -> shade_rays -> add -> resolve is DeviceScene.render's frame bit for bit,
+    in one pass or in sample passes and row bands.  Every call is one launch on ``stream`` (a HIP
+    stream handle; default torch's current stream) with no host synchronisation."""
+
+    def __init__(self, width: int, height: int, device: int = 0):
+        h = C.c_void_p()
+        check(lib().rt_film_create(int(device), int(width), int(height), C.byref(h)))
+        self._h = h
+        self.width, self.height, self.device = int(width), int(height), int(device)
+
+    def _handle(self) -> C.c_void_p:
+        if not self._h:
+            raise L.RTError(-1, "film is closed")
+        return self._h
+
+    def _stream(self, stream):
+        import torch
+
+        return torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream if stream is None else stream
+
+    def add(self, radiance, row0: int = 0, rows: Optional[int] = None, nsamples: Optional[int] = None,
+            stream: Optional[int] = None) -> None:
+        """Add ``nsamples`` samples per pixel of rows [row0, row0 + rows) (default: to the last row):
+        ``radiance`` is a float32 tensor on the film's device of rows*W*nsamples*3 elements, sample s
+        of pixel (x, y) at ((y - row0) * W + x) * nsamples + s, the order of camera_rays and of
+        shade_rays' output.  ``nsamples`` None: what the tensor's size gives."""
+        import torch
+
+        if rows is None:
+            rows = self.height - int(row0)
+        dev = torch.device("cuda", self.device)
+        if radiance.device != dev or radiance.dtype != torch.float32:
+            raise ValueError(f"Film.add: expects a float32 tensor on {dev}")
+        radiance = radiance.contiguous()
+        px = self.width * int(rows) * 3
+        if nsamples is None:
+            nsamples = radiance.numel() // px if px > 0 else 1
+        if radiance.numel() != px * int(nsamples):
+            raise ValueError("Film.add: radiance must hold rows * W * nsamples * 3 floats")
+        # (an empty tensor has no address: the C checks still answer for rows == 0)
+        p = radiance.data_ptr() if radiance.numel() else torch.empty(1, dtype=torch.float32, device=dev).data_ptr()
+        check(lib().rt_film_add_device(self._handle(), p, int(row0), int(rows), int(nsamples), self._stream(stream)))
+
+    def resolve(self, row0: int = 0, rows: Optional[int] = None, p6: bool = False, stream: Optional[int] = None):
+        """The pixels of rows [row0, row0 + rows) from the sums so far: a (rows, W, 3) float32
+        tensor, or with ``p6=True`` ``(rgb, bytes)``, bytes a (rows, W, 3) uint8 tensor of P6
+        samples (write_p6 defaults).  The rows must hold the same, non-zero number of samples.
+        Does not clear."""
+        import torch
+
+        if rows is None:
+            rows = self.height - int(row0)
+        dev = torch.device("cuda", self.device)
+        shape = (max(int(rows), 0), self.width, 3)
+        rgb = torch.empty(shape, dtype=torch.float32, device=dev)
+        b = torch.empty(shape, dtype=torch.uint8, device=dev) if p6 else None
+        spare = torch.empty(1, dtype=torch.float32, device=dev) if rgb.numel() == 0 else None
+        check(lib().rt_film_resolve_device(self._handle(), int(row0), int(rows),
+                                           rgb.data_ptr() if spare is None else spare.data_ptr(),
+                                           None if b is None or spare is not None else b.data_ptr(), self._stream(stream)))
+        return (rgb, b) if p6 else rgb
+
+    def clear(self, stream: Optional[int] = None) -> None:
+        """Sums and every row's sample count to 0."""
+        check(lib().rt_film_clear_device(self._handle(), self._stream(stream)))
+
+    def row_samples(self, row: int) -> int:
+        """Samples added to that row since the film was made or cleared."""
+        n = C.c_int64()
+        check(lib().rt_film_row_samples(self._handle(), int(row), C.byref(n)))
+        return int(n.value)
+
+    def close(self) -> None:
+        if self._h:
+            lib().rt_film_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def film_pixels_host(radiance, width: int, rows: int, nsamples: int, sums=None, count_after: Optional[int] = None):
+    """Host build of the film's arithmetic (rt_film_pixels_host, no device): adds ``radiance``
+    (rows*width*nsamples*3 float32, sample s of pixel p at p*nsamples + s) to the running ``sums``
+    ((rows, width, 3) float32, updated in place; None: zeros) and returns ``(sums, rgb)``, rgb the
+    pixels of ``count_after`` samples per pixel (default ``nsamples``: a film's first add)."""
+    r = _c(radiance, np.float32).reshape(-1)
+    width, rows, nsamples = int(width), int(rows), int(nsamples)
+    if r.size != max(width * rows * nsamples * 3, 0):
+        raise ValueError("film_pixels_host: radiance must hold rows * width * nsamples * 3 floats")
+    if sums is None:
+        sums = np.zeros((max(rows, 0), max(width, 0), 3), np.float32)
+    if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.flags.c_contiguous
+            and sums.size == max(rows * width * 3, 0)):
+        raise ValueError("film_pixels_host: sums must be a contiguous (rows, width, 3) float32 array")
+    rgb = np.zeros(sums.shape, np.float32)
+    spare = np.zeros(1, np.float32)  # (an empty array still has an address for the C checks)
+    check(lib().rt_film_pixels_host(ptr(r if r.size else spare), width, rows, nsamples, ptr(sums if sums.size else spare),
+                                    int(nsamples if count_after is None else count_after), ptr(rgb if rgb.size else spare)))
+    return sums, rgb
 
 
 def build_bvh(positions, indices):

@@ -1883,10 +1883,12 @@ extern "C" int rt_hit_record_host(const rt_ray* rays, const rt_triangle* tris, i
 
 // ---- camera rays (rt_query.hpp, camera_rays_kernel) --------------------------------------------
 namespace {
-// The checks of rt_camera_rays_host / _device: no HIP call before they pass.  *n_out: W * rows * spp.
-int camera_rays_args(const rt_camera* cam, int spp, int row0, int rows, const void* rays, size_t* n_out) {
+// The checks of rt_camera_rays[_pass]_host / _device: no HIP call before they pass.  spp: the
+// samples of this call, [sample0, sample0 + spp) of the frame's.  *n_out: W * rows * spp.
+int camera_rays_args(const rt_camera* cam, int sample0, int spp, int row0, int rows, const void* rays, size_t* n_out) {
     if (!cam || !rays) return set_error(RT_ERR_ARG, "rt_camera_rays: null camera or rays");
     if (spp < 1) return set_error(RT_ERR_ARG, "rt_camera_rays: spp < 1");
+    if (sample0 < 0 || sample0 > INT32_MAX - spp) return set_error(RT_ERR_ARG, "rt_camera_rays: sample0 < 0 or past 2^31-1");
     const int W = cam->pixel_width, H = cam->pixel_height;
     if (W < 1 || H < 1) return set_error(RT_ERR_ARG, "rt_camera_rays: an empty image");
     if (row0 < 0 || rows < 0 || row0 > H || rows > H - row0) return set_error(RT_ERR_ARG, "rt_camera_rays: rows outside the image");
@@ -1897,11 +1899,14 @@ int camera_rays_args(const rt_camera* cam, int spp, int row0, int rows, const vo
 }
 }  // namespace
 
-extern "C" int rt_camera_rays_host(const rt_camera* cam, int spp, const float* jitter, int row0, int rows, rt_ray* rays,
-                                   uint32_t* seeds) {
+extern "C" int rt_camera_rays_pass_host(const rt_camera* cam, int sample0, int spp, const float* jitter, int row0,
+                                        int rows, rt_ray* rays, uint32_t* seeds) {
     size_t n = 0;
-    int rc = camera_rays_args(cam, spp, row0, rows, rays, &n);
-    if (rc != RT_OK || n == 0) return rc;
+    int rc = camera_rays_args(cam, sample0, spp, row0, rows, rays, &n);
+    if (rc != RT_OK) return rc;
+    // (the default table is a whole frame's: a later slice of it is the caller's to cut)
+    if (!jitter && sample0 != 0) return set_error(RT_ERR_ARG, "rt_camera_rays_pass_host: null jitter with sample0 > 0");
+    if (n == 0) return RT_OK;
     std::vector<float> tab;
     if (!jitter) {
         tab.resize(size_t(2) * size_t(spp));
@@ -1920,15 +1925,20 @@ extern "C" int rt_camera_rays_host(const rt_camera* cam, int spp, const float* j
                 const f3 d = camera_dir(center, p00, du, dv, x, y, jitter[2 * s], jitter[2 * s + 1]);
                 rays[i].origin = cam->center;
                 rays[i].direction = rt_vec3{d.x, d.y, d.z};
-                if (seeds) seeds[i] = make_rng_seed(x, y, s);
+                if (seeds) seeds[i] = make_rng_seed(x, y, sample0 + s);
             }
     return RT_OK;
 }
 
-extern "C" int rt_camera_rays_device(int device, const rt_camera* cam, int spp, const float* jitter, int row0, int rows,
-                                     rt_ray* rays, uint32_t* seeds, void* stream) {
+extern "C" int rt_camera_rays_host(const rt_camera* cam, int spp, const float* jitter, int row0, int rows, rt_ray* rays,
+                                   uint32_t* seeds) {
+    return rt_camera_rays_pass_host(cam, 0, spp, jitter, row0, rows, rays, seeds);
+}
+
+extern "C" int rt_camera_rays_pass_device(int device, const rt_camera* cam, int sample0, int spp, const float* jitter,
+                                          int row0, int rows, rt_ray* rays, uint32_t* seeds, void* stream) {
     size_t n = 0;
-    int rc = camera_rays_args(cam, spp, row0, rows, rays, &n);
+    int rc = camera_rays_args(cam, sample0, spp, row0, rows, rays, &n);
     if (rc != RT_OK) return rc;
     if (!jitter) return set_error(RT_ERR_ARG, "rt_camera_rays_device: null jitter table");
     if (n == 0) return RT_OK;
@@ -1943,6 +1953,7 @@ extern "C" int rt_camera_rays_device(int device, const rt_camera* cam, int spp, 
     P.W = cam->pixel_width;
     P.spp = spp;
     P.row0 = row0;
+    P.sample0 = sample0;
     P.n = uint32_t(n);
     P.jitter = jitter;
     P.rays = reinterpret_cast<float*>(rays);
@@ -1950,6 +1961,11 @@ extern "C" int rt_camera_rays_device(int device, const rt_camera* cam, int spp, 
     hipLaunchKernelGGL(camera_rays_kernel, dim3((P.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P);
     HIP_TRY(hipGetLastError());
     return RT_OK;
+}
+
+extern "C" int rt_camera_rays_device(int device, const rt_camera* cam, int spp, const float* jitter, int row0, int rows,
+                                     rt_ray* rays, uint32_t* seeds, void* stream) {
+    return rt_camera_rays_pass_device(device, cam, 0, spp, jitter, row0, rows, rays, seeds, stream);
 }
 
 void rt::scene_set_caller_ordered(rt_scene* s, bool on) {

@@ -253,6 +253,7 @@ __global__ __launch_bounds__(BLOCK) void trace_hits_kernel(HitsParams Q) {
 struct CameraRaysParams {
     f3 center, p00, du, dv;
     int32_t W, spp, row0;
+    int32_t sample0;  // the table's first sample is sample0 of the frame's (rt_camera_rays_pass_device)
     uint32_t n;  // W * rows * spp < 2^31
     const float* __restrict__ jitter;  // 2 * spp
     float* __restrict__ rays;          // n x rt_ray
@@ -277,5 +278,5 @@ __global__ __launch_bounds__(BLOCK) void camera_rays_kernel(CameraRaysParams P) 
     R[3] = d.x;
     R[4] = d.y;
     R[5] = d.z;
-    if (P.seeds != nullptr) P.seeds[i] = make_rng_seed(x, y, s);
+    if (P.seeds != nullptr) P.seeds[i] = make_rng_seed(x, y, P.sample0 + s);
 }
