@@ -9,6 +9,7 @@ reference's own code: jitter tables, ray-triangle KAT answers, camera bases, sce
     python tests/golden/gen_golden.py            # all fixtures
     python tests/golden/gen_golden.py --only c3_small
     python tests/golden/gen_golden.py --only 'shade_*'
+    python tests/golden/gen_golden.py --only 'ties_*'
 """
 from __future__ import annotations
 
@@ -220,6 +221,38 @@ def gen_shade(name: str) -> None:
         (dst / "meta.json").write_text(json.dumps(meta, indent=1) + "\n")
 
 
+def ties_cases() -> dict:
+    sys.path.insert(0, str(HERE.parent))
+    import tie_scenes
+
+    return {"ties_" + n: n for n in tie_scenes.FRAME_CASES}
+
+
+def gen_ties(name: str) -> None:
+    """A coplanar lattice frame (tests/tie_scenes.py: ties at the winning t decided by the visiting
+    order) through the reference render() and SearchBVH (ref_g arrays, miss colour 0); frame, hits
+    and t kept."""
+    sys.path.insert(0, str(HERE.parent))
+    import shade_fuzz
+    import tie_scenes
+
+    c = tie_scenes.frame_case(name)
+    dst = HERE / "scenes" / ("ties_" + name)
+    dst.mkdir(parents=True, exist_ok=True)
+    with tempfile.TemporaryDirectory() as td:
+        t = Path(td)
+        shade_fuzz.write_arrays(c, t)
+        run([REF / "ref_g", "arrays", t, t, c["W"], c["H"], c["spp"], c["depth"], 1 if c["diffuse"] else 0])
+        meta = json.loads((t / "meta.json").read_text())
+        meta["generator"] = "tests/tie_scenes.py frame_case(%r)" % name
+        meta["num_materials"] = int(c["mats"].size)
+        meta["sha256"] = {k: sha256(t / k) for k in (*shade_fuzz.INPUTS, "fb.f32", "hits.i32", "hitt.f32")}
+        assert {k: meta["sha256"][k] for k in shade_fuzz.INPUTS} == shade_fuzz.input_sha256(c)
+        for k in ("fb.f32", "hits.i32", "hitt.f32"):
+            gz(t / k, dst / (k + ".gz"))
+        (dst / "meta.json").write_text(json.dumps(meta, indent=1) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*")
@@ -238,6 +271,9 @@ def main() -> None:
     for full, n in shade_cases().items():
         if not want or any(fnmatch.fnmatchcase(full, w) for w in want):
             gen_shade(n)
+    for full, n in ties_cases().items():
+        if not want or any(fnmatch.fnmatchcase(full, w) for w in want):
+            gen_ties(n)
     if not want or "jitter" in want:
         gen_jitter()
     if not want or "kat" in want:

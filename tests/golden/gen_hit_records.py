@@ -2,7 +2,7 @@
 
     python tests/golden/gen_hit_records.py [--driver oracle/_ref/ref_hit_records]
 
-For each scene of tests/hit_records.py NAMES: the first 64 rays of each class of its 4096-ray batch
+For each scene of tests/hit_records.py NAMES and for the small lattice scene of tests/tie_scenes.py: the first 64 rays of each class of its 4096-ray batch
 go, with the scene's nodes, aabbs and triangles, through tests/native/ref_hit_records.cpp (the
 reference's SearchBVH; compile it as its header says), and the HitRecord fields come back as raw
 little-endian arrays, stored gzipped; meta.json keeps their sha256 and the commands.
@@ -25,6 +25,7 @@ for p in (REPO, REPO / "tests"):
     if str(p) not in sys.path:
         sys.path.insert(0, str(p))
 import hit_records as hr  # noqa: E402
+import tie_scenes as ts  # noqa: E402
 
 COMPILE = ("g++ -std=c++17 -O2 -ffp-contract=off -fno-fast-math -w -D__device__= -I$G/include -I$G/src "
            "-I$G/third_party/glm tests/native/ref_hit_records.cpp -x c++ $G/include/bvh.cu $G/include/query.cu "
@@ -40,9 +41,10 @@ def main() -> None:
             "command": "ref_hit_records <indir> <outdir>   (per scene: nodes.bin, aabbs.bin, tris.bin, rays.f32)",
             "rays": f"tests/hit_records.py batch(name)['rays'][fixture_pick()]: the first {hr.PER_CLASS} of each class",
             "fuzz_case": hr.FUZZ_CASE, "fuzz_ray_seed": hr.FUZZ_RAY_SEED, "sha256": {}, "hits": {}}
-    for name in hr.NAMES:
-        s = hr.scene(name)
-        rays = np.ascontiguousarray(hr.batch(name)["rays"][pick], np.float32)
+    for name in hr.NAMES + (ts.HIT_RECORDS_NAME,):
+        lattice = name == ts.HIT_RECORDS_NAME  # (its classes V, E, L, R are quarters of the batch as well)
+        s = ts.scene("small") if lattice else hr.scene(name)
+        rays = np.ascontiguousarray((ts.batch("small") if lattice else hr.batch(name))["rays"][pick], np.float32)
         out = hr.GOLDEN_DIR / name
         out.mkdir(parents=True, exist_ok=True)
         with tempfile.TemporaryDirectory() as td:
