@@ -424,7 +424,8 @@ int rt_render_hw1_ex(int device, const rt_vec3* positions, const rt_vec3* normal
  * and uploaded once, the binning buffers kept.  rt_render_hw1_device renders one frame on
  * hip_stream (NULL = the default stream) without synchronising: rgb_dev (W*H*3 floats) and/or
  * p6_dev (W*H*3 bytes, write_p6 defaults) and the optional AOVs (W*H*spp each) are device
- * pointers; jitter NULL = jittered_samples(spp, 42) in [0,1).  rt_hw1_kernel_times: ms of the
+ * pointers; jitter NULL = jittered_samples(spp, 42) in [0,1); a caller's table with an entry
+ * outside [0,1) takes the brute-force kernel (exact for every table).  rt_hw1_kernel_times: ms of the
  * frame's kernels (events around them) for the latest min(max, frames, 64) frames, oldest first;
  * rt_hw1_kernel_name: the render kernel the latest frame launched, as rocprofv3 names it. */
 typedef struct rt_hw1_scene rt_hw1_scene;
@@ -451,6 +452,29 @@ const char* rt_hw1_kernel_name(const rt_hw1_scene* s);
  * total above the capacity its frame ran with means that frame's overflowing tiles took the
  * brute-force loop; the next frame runs with a grown list. */
 int rt_hw1_list_info(const rt_hw1_scene* s, int64_t info[2]);
+
+/* The binned path's per-triangle bounds and their read-back, for tests.
+ * The bounds assume the sample positions ix = (int)(x + jx) in {x, x + 1}, that is a jitter table
+ * in [0,1).  rt_render_hw1_device and rt_render_hw1_ex therefore render a caller's table with any
+ * entry outside [0,1) (NaN included) with the brute-force kernel, which is exact for every table;
+ * rt_hw1_kernel_name says which kernel a frame took.
+ * rt_hw1_rects_host: host build of the bounds (no device needed, like rt_powf_host), through the
+ *   functions the count pass runs: per triangle k, rects[4k..] = (ix_lo, iy_lo, ix_hi, iy_hi), the
+ *   integer pixel positions whose camera ray ray_intersection may accept (lo > hi: none), and
+ *   tiles[4k..] = (tx0, tx1, ty0, ty1), the 16x4-pixel wave tiles listed for it, inclusive; an
+ *   empty range is (0, -1, 0, -1).
+ * rt_hw1_debug_bins: what the latest rt_render_hw1_device frame left in the scene's binning
+ *   buffers (waits for that frame; RT_ERR_ARG when it took the brute-force kernel).  info =
+ *   {triangles, tiles, list total, 1 if the total fits the capacity the frame ran with, else 0:
+ *   tiles whose list ends past the capacity were not written}.  Each output may be NULL: rects
+ *   4 * triangles ints, offsets tiles + 1 entries (offsets_cap: entries it holds), list
+ *   min(total, capacity) triangle indices (list_cap: entries it holds), tile t's at
+ *   [offsets[t], offsets[t + 1]) in the order the atomics gave.  Call with NULL outputs to size.
+ * (Additive to ABI 3: rt_hw1_rects_host, rt_hw1_debug_bins.) */
+int rt_hw1_rects_host(const rt_camera* cam, const rt_vec3* positions, const uint32_t* indices, size_t num_triangles,
+                      int32_t* rects, int32_t* tiles);
+int rt_hw1_debug_bins(rt_hw1_scene* s, int64_t info[4], int32_t* rects, uint32_t* offsets, size_t offsets_cap,
+                      uint32_t* list, size_t list_cap);
 
 /* Batched ray-triangle queries on the GPU (one triangle, n rays from `origin`), the device
  * Möller–Trumbore used by the kernels:  hw1 != 0 -> HW1 ray_intersection

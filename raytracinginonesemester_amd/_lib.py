@@ -197,6 +197,8 @@ SIGNATURES = {
     "rt_hw1_kernel_times": (I, [P, P, I, P]),
     "rt_hw1_kernel_name": (C.c_char_p, [P]),
     "rt_hw1_list_info": (I, [P, P]),
+    "rt_hw1_rects_host": (I, [P, P, P, SZ, P, P]),
+    "rt_hw1_debug_bins": (I, [P, P, P, P, SZ, P, SZ]),
     "rt_intersect_rays": (I, [I, P, P, P, I, I, C.c_float, C.c_float, P, P]),
     "rt_trace_rays_device": (I, [P, I, P, P, SZ, I, P, P, P]),
     "rt_trace_rays": (I, [P, I, P, P, SZ, I, P, P, P]),

@@ -757,6 +757,17 @@ def render_hw1(positions, normals, indices, camera: Camera, light_position, ligh
     return out if len(out) > 1 else out[0]
 
 
+def hw1_rects_host(positions, indices, camera: Camera):
+    """Host build of the binned HW1 path's per-triangle bounds (rt_hw1_rects_host; no device):
+    rects (P, 4) int32 (ix_lo, iy_lo, ix_hi, iy_hi) and tiles (P, 4) int32 (tx0, tx1, ty0, ty1),
+    the inclusive range of 16x4-pixel tiles the triangle is listed in; empty: tx1 < tx0."""
+    pos, idx = _c(positions, np.float32), _c(indices, np.uint32)
+    n = idx.size // 3
+    rects, tiles = np.zeros((n, 4), np.int32), np.zeros((n, 4), np.int32)
+    check(lib().rt_hw1_rects_host(C.byref(camera.c), ptr(pos), ptr(idx), n, ptr(rects), ptr(tiles)))
+    return rects, tiles
+
+
 class HW1Scene:
     """A HW1 mesh resident on one MI355X (rt_hw1_scene): repeated frames of the HW1 path
     (HW1/src/render.cpp:72-116) without re-uploading it."""
@@ -803,6 +814,21 @@ class HW1Scene:
         info = (C.c_int64 * 2)()
         check(lib().rt_hw1_list_info(self._h, info))
         return int(info[0]), int(info[1])
+
+    def bins(self) -> dict:
+        """The binning state of the latest render_device frame (rt_hw1_debug_bins; waits for it):
+        rects (P, 4) int32, offsets (tiles + 1) uint32, list (min(total, capacity)) uint32, total,
+        complete (False: the total exceeded the capacity, so some tiles' lists were not written)."""
+        info = (C.c_int64 * 4)()
+        check(lib().rt_hw1_debug_bins(self._h, info, None, None, 0, None, 0))
+        n, tiles, total = int(info[0]), int(info[1]), int(info[2])
+        rects = np.zeros((n, 4), np.int32)
+        offsets = np.zeros(tiles + 1, np.uint32)
+        lst = np.zeros(total, np.uint32)  # (at least the entries written)
+        check(lib().rt_hw1_debug_bins(self._h, info, ptr(rects), ptr(offsets), offsets.size, ptr(lst), lst.size))
+        written = total if info[3] else min(total, self.list_info()[0])
+        return {"rects": rects, "offsets": offsets, "list": lst[:written], "total": int(info[2]),
+                "complete": bool(info[3])}
 
     def close(self) -> None:
         if self._h:

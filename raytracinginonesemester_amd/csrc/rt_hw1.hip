@@ -227,13 +227,13 @@ __global__ __launch_bounds__(BLOCK) void render_hw1_kernel(Hw1Params P) {
 // a half-plane in (ix, iy); the rectangle is the bounding box (+1 pixel) of the padded image
 // rectangle clipped by the four half-planes.  Degenerate cases (tiny tnum, huge magnitudes,
 // an image whose directions reach 0) get the whole image.
-__device__ __forceinline__ void hw1_cross_d(const double a[3], const double b[3], double r[3]) {
+__host__ __device__ __forceinline__ void hw1_cross_d(const double a[3], const double b[3], double r[3]) {
     r[0] = a[1] * b[2] - a[2] * b[1];
     r[1] = a[2] * b[0] - a[0] * b[2];
     r[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-__device__ int4 hw1_rect(const Hw1Params& P, int k) {
+__host__ __device__ int4 hw1_rect(const Hw1Params& P, int k) {
     const int X0 = -2, X1 = P.W + 1, Y0 = -2, Y1 = P.H + 1;  // ix in [x, x+1] (truncation)
     const int4 all = make_int4(X0, Y0, X1, Y1), none = make_int4(1, 1, 0, 0);
     const float4 A = P.tri[3 * (size_t)k], B = P.tri[3 * (size_t)k + 1], Cq = P.tri[3 * (size_t)k + 2];
@@ -361,7 +361,7 @@ __device__ int4 hw1_rect(const Hw1Params& P, int k) {
 // independent of the visiting order.  (A NaN t is never below or equal to anything, in
 // either form.)
 constexpr int HW1_TW = 16, HW1_TH = 4;  // wave tile: 16 x 4 pixels
-__device__ __forceinline__ bool hw1_tile_range(const Hw1Params& P, int4 r, int& tx0, int& tx1, int& ty0, int& ty1) {
+__host__ __device__ __forceinline__ bool hw1_tile_range(const Hw1Params& P, int4 r, int& tx0, int& tx1, int& ty0, int& ty1) {
     const int tiles_x = (P.W + HW1_TW - 1) / HW1_TW, tiles_y = (P.H + HW1_TH - 1) / HW1_TH;
     if (r.x > r.z || r.y > r.w) return false;
     tx0 = max(0, r.x - 1) / HW1_TW;
@@ -818,6 +818,7 @@ struct rt_hw1_scene {
         uint64_t last_frame = 0;
         bool used = false;
         int chunk_log2 = -1;       // the item size the chunk table is laid out for
+        bool last_binned = false;  // the lane's latest frame ran the binning passes (rt_hw1_debug_bins)
     };
     static constexpr int kLanes = 8;
     Lane lane[kLanes];
@@ -980,7 +981,12 @@ static int render_frame(rt_hw1_scene* s, int li, const rt_camera* cam, rt_vec3 l
         s->jitter_host = tab;
     }
     if (!have_default) s->jitter_default = jitter == nullptr;
-    const bool brute = (flags & RT_HW1_BRUTE) != 0;
+    // hw1_rect bounds the positions ix = (int)(x + j) in {x, x + 1}, that is j in [0,1): a caller's
+    // table with any other entry (NaN included) takes the brute-force kernel, exact for every table
+    bool in_unit = true;
+    for (size_t i = 0; jitter && i < 2 * size_t(spp); ++i)
+        if (!(jitter[i] >= 0.0f && jitter[i] < 1.0f)) in_unit = false;
+    const bool brute = (flags & RT_HW1_BRUTE) != 0 || !in_unit;
     const int ntiles = ((W + HW1_TW - 1) / HW1_TW) * ((H + HW1_TH - 1) / HW1_TH);
     // the list total of the latest frame whose scan has run (each total carries its frame's tag:
     // read from pinned memory, no runtime call)
@@ -1125,6 +1131,7 @@ static int render_frame(rt_hw1_scene* s, int li, const rt_camera* cam, rt_vec3 l
     HIP_TRY(hipGetLastError());
     L.used = true;
     L.last_stream = st;
+    L.last_binned = !brute;
     L.last_frame = s->frames;
     s->frames++;
     return RT_OK;
@@ -1278,6 +1285,74 @@ extern "C" int rt_hw1_list_info(const rt_hw1_scene* s, int64_t info[2]) {
         info[0] = s->lane[s->lane_of[sl]].list_cap;
         HIP_TRY(hipEventSynchronize(s->end_of(sl)));
         info[1] = uint32_t(s->total_host[sl]);
+    }
+    return RT_OK;
+}
+
+// Host build of the binning's per-triangle bounds (no device): the mesh packed as
+// rt_hw1_scene_create packs it, the camera bounds as render_frame makes them, then hw1_rect and
+// hw1_tile_range, the functions hw1_rect_count_kernel runs.
+extern "C" int rt_hw1_rects_host(const rt_camera* cam, const rt_vec3* pos, const uint32_t* idx, size_t P,
+                                 int32_t* rects, int32_t* tiles) {
+    if (!cam || !pos || !idx || !rects || !tiles) return set_error(RT_ERR_ARG, "rt_hw1_rects_host: null argument");
+    if (cam->pixel_width < 1 || cam->pixel_height < 1) return set_error(RT_ERR_ARG, "camera has no pixels");
+    if (P > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "too many triangles");
+    std::vector<float4> ht(3 * P);
+    for (size_t k = 0; k < P; ++k) {
+        const rt_vec3 a = pos[idx[3 * k]], b = pos[idx[3 * k + 1]], c = pos[idx[3 * k + 2]];
+        ht[3 * k] = make_float4(a.x, a.y, a.z, 0.f);
+        ht[3 * k + 1] = make_float4(b.x - a.x, b.y - a.y, b.z - a.z, 0.f);
+        ht[3 * k + 2] = make_float4(c.x - a.x, c.y - a.y, c.z - a.z, 0.f);
+    }
+    Hw1Params hp{};
+    hp.tri = ht.data();
+    hp.num_tris = int32_t(P);
+    hp.center = f3{cam->center.x, cam->center.y, cam->center.z};
+    hp.W = cam->pixel_width;
+    hp.H = cam->pixel_height;
+    const float c3[3] = {cam->center.x, cam->center.y, cam->center.z};
+    const float p3[3] = {cam->pixel00_loc.x, cam->pixel00_loc.y, cam->pixel00_loc.z};
+    const float u3[3] = {cam->pixel_delta_u.x, cam->pixel_delta_u.y, cam->pixel_delta_u.z};
+    const float v3[3] = {cam->pixel_delta_v.x, cam->pixel_delta_v.y, cam->pixel_delta_v.z};
+    hp.cb = hw1_cam_bounds(c3, p3, u3, v3, hp.W, hp.H);
+    for (size_t k = 0; k < P; ++k) {
+        const int4 r = hw1_rect(hp, int(k));
+        int tx0 = 0, tx1 = -1, ty0 = 0, ty1 = -1;
+        if (!hw1_tile_range(hp, r, tx0, tx1, ty0, ty1)) tx0 = ty0 = 0, tx1 = ty1 = -1;
+        const int32_t rr[4] = {r.x, r.y, r.z, r.w}, tt[4] = {tx0, tx1, ty0, ty1};
+        std::memcpy(rects + 4 * k, rr, sizeof rr);
+        std::memcpy(tiles + 4 * k, tt, sizeof tt);
+    }
+    return RT_OK;
+}
+
+// The binning state the latest direct frame left on lane 0 (a test's read-back).
+extern "C" int rt_hw1_debug_bins(rt_hw1_scene* s, int64_t info[4], int32_t* rects, uint32_t* offsets,
+                                 size_t offsets_cap, uint32_t* list, size_t list_cap) {
+    if (!s || !info) return set_error(RT_ERR_ARG, "rt_hw1_debug_bins: null argument");
+    const rt_hw1_scene::Lane& L = s->lane[0];
+    if (!L.used || !L.last_binned || L.bins_tiles < 1)
+        return set_error(RT_ERR_ARG, "rt_hw1_debug_bins: the latest direct frame did not run the binning passes");
+    DeviceGuard g(s->device);
+    HIP_TRY(hipEventSynchronize(s->frame_end(L.last_frame)));
+    const size_t nt = size_t(L.bins_tiles);
+    // counts | cursor | done | arrive | offsets (render_frame's layout)
+    const uint32_t* doff = static_cast<const uint32_t*>(L.bins.p) + 3 * nt + 1;
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpy(&total, doff + nt, sizeof total, hipMemcpyDeviceToHost));
+    info[0] = int64_t(s->P);
+    info[1] = int64_t(nt);
+    info[2] = total;
+    info[3] = total <= L.list_cap ? 1 : 0;
+    if (rects) HIP_TRY(hipMemcpy(rects, L.rects.p, s->P * sizeof(int4), hipMemcpyDeviceToHost));
+    if (offsets) {
+        if (offsets_cap < nt + 1) return set_error(RT_ERR_ARG, "rt_hw1_debug_bins: offsets_cap below tiles + 1");
+        HIP_TRY(hipMemcpy(offsets, doff, (nt + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (list) {
+        const size_t n = std::min<size_t>(total, L.list_cap);
+        if (list_cap < n) return set_error(RT_ERR_ARG, "rt_hw1_debug_bins: list_cap below the list's entries");
+        if (n) HIP_TRY(hipMemcpy(list, L.list.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return RT_OK;
 }

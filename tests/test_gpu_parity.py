@@ -487,7 +487,14 @@ def _soup(rng, n, kind):
 @pytest.mark.parametrize("spp", [1, 4])
 def test_hw1_binned_equals_brute_force_fuzz(kind, spp):
     """The binned HW1 kernel skips triangles by a conservative pixel rectangle: it must return
-    the brute-force loop's winner (first index with the smallest t) bit for bit."""
+    the brute-force loop's winner (first index with the smallest t) bit for bit.
+
+    What this can and cannot see (measured with the oracle, a triangle at a time): a frame checks
+    a rectangle only where its triangle wins the pixel, and a 400-triangle mixed soup has 12
+    distinct winners; the edge_on and slivers soups accept next to nothing (0 and 4 samples of
+    120 triangles at 96x72x4).  The sharp test is the per-triangle one,
+    tests/test_hw1_rects_host.py, with tests/test_gpu_hw1_binning.py for the device's
+    rectangles and lists."""
     rng = np.random.default_rng({"mixed": 1, "edge_on": 2, "around": 3, "slivers": 4}[kind] * 10 + spp)
     pos, nrm, idx, cam_pos = _soup(rng, 3000, kind)
     cam = rt.Camera(tuple(cam_pos), (0.0, 0.0, 0.2), (0.0, 0.0, 1.0), 30.0, 24.0, 96, 72, hw1=True)
