@@ -36,7 +36,11 @@ extern "C" {
                                  rt_film_create, rt_film_destroy, rt_film_clear_device,
                                  rt_film_add_device, rt_film_resolve_device, rt_film_row_samples,
                                  rt_film_pixels_host, rt_camera_rays_pass_host,
-                                 rt_camera_rays_pass_device */
+                                 rt_camera_rays_pass_device; rt_path_state, rt_path_opts, RT_PATH_LAST,
+                                 RT_PATH_NONE, rt_path_opts_default, rt_path_begin_device,
+                                 rt_path_step_device, rt_path_step_variant, rt_path_step_host,
+                                 rt_path_compact_scratch_bytes, rt_path_compact_device,
+                                 rt_path_finish_device */
 
 enum {
     RT_OK = 0,
@@ -684,6 +688,96 @@ int rt_film_row_samples(const rt_film* f, int row, int64_t* count);
  * writes the pixels of count_after samples per pixel, the count after this add (>= nsamples). */
 int rt_film_pixels_host(const float* radiance, int width, int rows, int nsamples, float* sum_inout,
                         int64_t count_after, float* rgb_out);
+
+/* ---- path stages for caller hits -------------------------------------------------------------
+ * The body of TraceRayIterative's depth loop (G/include/query.h:178-217) as a stage of its own
+ * (DESIGN.md §4.21), for callers who change the surface between the trace and the shading: it
+ * works on caller rays and hit records (rt_trace_hits' or the caller's own: only tri, p, normal
+ * and material of a record are read) with an optional material per hit, and brings the library's
+ * direct lighting, shadow rays and bounce to them.  A path runs as
+ *   begin; repeat { rt_trace_hits_device -> [edit hits / pick materials] -> step -> compact }; finish
+ * and with nothing edited its radiance is rt_shade_rays', and so the reference's, bit for bit.
+ * All pointers are device pointers on the scene's (or `device`'s) device; every call is
+ * asynchronous on hip_stream (NULL = the null stream) and ordered with the others of that stream.
+ * There are no host-array forms: staged paths are a device-resident pipeline, rt_shade_rays is
+ * the one-call form.
+ *
+ * The state of N paths, indexed by path id: radiance 3N floats, throughput 3N floats, rng N words.
+ * rt_path_begin_device: radiance 0, throughput 1, rng[i] = seeds_dev ? seeds_dev[i] : 42u, the
+ *   state at the top of TraceRayIterative (query.h:166-170).
+ * rt_path_step_device: the loop body for entries k < m.  Entry k belongs to path
+ *   id = ids_dev ? ids_dev[k] : k.  Ids are the caller's to keep unique within a call and below N:
+ *   each state word then has one writer (plain stores, no atomics).  An id of RT_PATH_NONE marks an
+ *   entry that carries no path (a path that ended, in a batch that is not compacted): no state
+ *   word is read or written, alive[k] = 0, direct = 0, and its ray is copied to next_rays_dev[k].
+ *   - hits[k].tri < 0 is a miss: radiance += throughput * miss_color, alive[k] = 0, direct = 0.
+ *   - The material is mats_dev ? mats_dev[k] (13 floats, read through a 4-byte aligned pointer)
+ *     : what assignMaterialToHit gives for the record (query.h:134-153): the scene's table entry
+ *     hits[k].material, or the Material() defaults when that index is outside the table (-1).
+ *   - ShadeDirect (G/include/shader.h:65-110) from the record: N = unit(hit.normal),
+ *     V = unit(ray.origin - hit.p), ambient and emission of the material, then per scene light the
+ *     NdotL > 0 test, IsInShadow's shadow ray (any-hit, bounded by the light's distance, skipped
+ *     when that distance is <= 0) and EvaluateBRDF on the record's normal as stored.
+ *     radiance += throughput * direct; direct_dev[3k..3k+2], when not NULL, receives ShadeDirect's
+ *     value itself.
+ *   - Unless opt->flags has RT_PATH_LAST, the bounce of query.h:193-216 with that material: the path
+ *     ends on kd + kr <= 0; otherwise rng_next is drawn, then the diffuse (opt->diffuse_bounce and
+ *     xi < kd / (kd + kr)) or the mirror ray and throughput, then the 1e-4 cut-off.  alive[k] = 1
+ *     exactly when the reference's loop would go on to trace the new ray, which is then
+ *     next_rays_dev[k]; a dead entry gets its input ray copied there, so every byte of
+ *     next_rays_dev and alive_dev is written.  next_rays_dev may be rays_dev itself.
+ *   - RT_PATH_LAST (a path's last depth): no bounce, no draw; next_rays_dev and alive_dev may be
+ *     NULL (they are required otherwise), and alive_dev, when given, is written 0 throughout.
+ *   Variant rule as for the queries (WIDE; BINARY with RT_FLAG_BINARY; DEEP), 16-byte alignment of
+ *   hits_dev as for rt_trace_hits_device.  m == 0 is RT_OK with no launch; m > 2^31-1 is
+ *   RT_ERR_UNSUPPORTED; a null scene, rays, hits, opt or state (or state member) is RT_ERR_ARG, and
+ *   so is a flag bit other than RT_FLAG_BINARY | RT_PATH_LAST.  Every argument check runs before
+ *   any HIP call.  Like a query the step reads only the scene's immutable arrays, takes no part in
+ *   the frame ordering and may run on any stream beside frames of the same scene, of a clone or
+ *   of an rt_renderer's scene.  It terminates for any bit patterns (per light one DFS that visits
+ *   a node at most once; the bounce draws as rt_shade_rays does).
+ * rt_path_compact_device: stable compaction.  For the k < m with alive_dev[k] != 0, in increasing
+ *   k, rays_in_dev[k] and the id (ids_in_dev ? ids_in_dev[k] : k) go to the next slot of
+ *   rays_out_dev / ids_out_dev (room for m entries each), and their number to *count_dev.
+ *   scratch_dev: rt_path_compact_scratch_bytes(m) bytes, 4-byte aligned.  The outputs must not
+ *   overlap the inputs (RT_ERR_ARG); any m up to 2^31-1 is accepted (above: RT_ERR_UNSUPPORTED);
+ *   m == 0 writes count 0 and reads nothing else.  Launches in stream order (tile counts, a scan of
+ *   the counts, scatter): no block waits for another.
+ * rt_path_finish_device: the reference's clamp (shader.h:24-32) on all 3n radiance floats, once
+ *   the paths are done: NaN and -0.0 stay as they are.
+ * rt_path_step_host: host build of the step's arithmetic (no device, no traversal), through the
+ *   function the kernel runs: host arrays, the scene's material table and lights passed as arrays
+ *   (table may be NULL with num_table 0), and occluded[k * num_lights + l], consulted exactly where
+ *   the kernel would cast entry k's shadow ray to light l (non-zero: in shadow).  hits needs no
+ *   alignment.  Same argument rules; only RT_PATH_LAST of opt->flags has a meaning here.
+ * (Additive to ABI 3: the names below.) */
+typedef struct { float* radiance; float* throughput; uint32_t* rng; } rt_path_state;
+typedef struct {
+    int32_t diffuse_bounce;
+    rt_vec3 miss_color;
+    int32_t flags;            /* RT_FLAG_BINARY | RT_PATH_LAST */
+} rt_path_opts;
+enum { RT_PATH_LAST = 16 };   /* a bit no RT_FLAG_* uses */
+#define RT_PATH_NONE 0xFFFFFFFFu
+void rt_path_opts_default(rt_path_opts* o);   /* 1, (0,0,0), 0 */
+
+int rt_path_begin_device(int device, size_t n, const uint32_t* seeds_dev, const rt_path_state* st, void* hip_stream);
+int rt_path_step_device(rt_scene* s, size_t m, const rt_ray* rays_dev, const rt_hit* hits_dev,
+                        const rt_material* mats_dev, const uint32_t* ids_dev, const rt_path_opts* opt,
+                        const rt_path_state* st, rt_ray* next_rays_dev, uint8_t* alive_dev, float* direct_dev,
+                        void* hip_stream);
+/* RT_RAYS_VARIANT_* of the latest rt_path_step_device call on s (NONE before the first), by
+ * rt_trace_rays_variant's rule; a word of its own. */
+int rt_path_step_variant(const rt_scene* s);
+int rt_path_step_host(size_t m, const rt_ray* rays, const rt_hit* hits, const rt_material* mats, const uint32_t* ids,
+                      const rt_material* table, int num_table, const rt_light* lights, int num_lights,
+                      const uint8_t* occluded, const rt_path_opts* opt, const rt_path_state* st, rt_ray* next_rays,
+                      uint8_t* alive, float* direct);
+size_t rt_path_compact_scratch_bytes(size_t m);
+int rt_path_compact_device(int device, size_t m, const uint8_t* alive_dev, const rt_ray* rays_in_dev,
+                           const uint32_t* ids_in_dev, rt_ray* rays_out_dev, uint32_t* ids_out_dev,
+                           uint32_t* count_dev, void* scratch_dev, void* hip_stream);
+int rt_path_finish_device(int device, size_t n, float* radiance_dev, void* hip_stream);
 
 /* The Blinn-Phong powf of the kernels (restatement of the reference libm's powf, see
  * csrc/rt_math.hpp): rt_powf_host evaluates the host build, rt_powf_batch the device build

@@ -234,6 +234,70 @@ inline std::vector<float> film_pixels_host(const std::vector<float>& radiance, i
     return rgb;
 }
 
+// Path stages for caller hits (rt_path_*): TraceRayIterative's loop body on caller rays and hit records,
+// with begin, compact and finish around it.  Device pointers; every call is asynchronous on hip_stream.
+inline rt_path_opts path_opts(bool diffuse_bounce = true, rt_vec3 miss_color = rt_vec3{0.f, 0.f, 0.f}, int flags = 0) {
+    rt_path_opts o;
+    rt_path_opts_default(&o);
+    o.diffuse_bounce = diffuse_bounce ? 1 : 0;
+    o.miss_color = miss_color;
+    o.flags = flags;
+    return o;
+}
+inline void path_begin(int device, size_t n, const uint32_t* seeds_dev, const rt_path_state& st, void* hip_stream = nullptr) {
+    check(rt_path_begin_device(device, n, seeds_dev, &st, hip_stream));
+}
+// mats_dev, ids_dev and direct_dev may be null; next_rays_dev and alive_dev too with RT_PATH_LAST in opt.flags.
+inline void path_step(const DeviceScene& ds, size_t m, const rt_ray* rays_dev, const rt_hit* hits_dev,
+                      const rt_material* mats_dev, const uint32_t* ids_dev, const rt_path_opts& opt, const rt_path_state& st,
+                      rt_ray* next_rays_dev, uint8_t* alive_dev, float* direct_dev = nullptr, void* hip_stream = nullptr) {
+    check(rt_path_step_device(ds.get(), m, rays_dev, hits_dev, mats_dev, ids_dev, &opt, &st, next_rays_dev, alive_dev,
+                              direct_dev, hip_stream));
+}
+// scratch_dev: rt_path_compact_scratch_bytes(m) bytes.
+inline void path_compact(int device, size_t m, const uint8_t* alive_dev, const rt_ray* rays_in_dev, const uint32_t* ids_in_dev,
+                         rt_ray* rays_out_dev, uint32_t* ids_out_dev, uint32_t* count_dev, void* scratch_dev,
+                         void* hip_stream = nullptr) {
+    check(rt_path_compact_device(device, m, alive_dev, rays_in_dev, ids_in_dev, rays_out_dev, ids_out_dev, count_dev,
+                                 scratch_dev, hip_stream));
+}
+inline void path_finish(int device, size_t n, float* radiance_dev, void* hip_stream = nullptr) {
+    check(rt_path_finish_device(device, n, radiance_dev, hip_stream));
+}
+
+// The step's arithmetic on the host (rt_path_step_host) over host vectors: the state of radiance.size() / 3
+// paths is updated in place; occluded holds rays.size() * lights.size() bytes, entry k's answer for light l at
+// k * lights.size() + l.  ids and mats may be empty (entry k is path k; the table's material of the record).
+struct PathStepHost {
+    std::vector<rt_ray> next_rays;
+    std::vector<uint8_t> alive;
+    std::vector<float> direct;
+};
+inline PathStepHost path_step_host(const std::vector<rt_ray>& rays, const std::vector<rt_hit>& hits,
+                                   const std::vector<rt_material>& mats, const std::vector<uint32_t>& ids,
+                                   const std::vector<rt_material>& table, const std::vector<rt_light>& lights,
+                                   const std::vector<uint8_t>& occluded, const rt_path_opts& opt,
+                                   std::vector<float>& radiance, std::vector<float>& throughput, std::vector<uint32_t>& rng) {
+    const size_t m = rays.size();
+    if (hits.size() != m || (!mats.empty() && mats.size() != m) || (!ids.empty() && ids.size() != m) ||
+        occluded.size() != m * lights.size() || radiance.size() != throughput.size() || radiance.size() != 3 * rng.size())
+        throw Error(RT_ERR_ARG, "path_step_host: the arrays do not match the batch");
+    for (uint32_t id : ids)
+        if (id != RT_PATH_NONE && id >= rng.size()) throw Error(RT_ERR_ARG, "path_step_host: a path id outside the state");
+    if (ids.empty() && m > rng.size()) throw Error(RT_ERR_ARG, "path_step_host: more entries than paths");
+    PathStepHost out;
+    out.next_rays.resize(m);
+    out.alive.resize(m);
+    out.direct.resize(3 * m);
+    if (m == 0) return out;
+    const rt_path_state st{radiance.data(), throughput.data(), rng.data()};
+    check(rt_path_step_host(m, rays.data(), hits.data(), mats.empty() ? nullptr : mats.data(), ids.empty() ? nullptr : ids.data(),
+                            table.empty() ? nullptr : table.data(), int(table.size()), lights.empty() ? nullptr : lights.data(),
+                            int(lights.size()), occluded.empty() ? nullptr : occluded.data(), &opt, &st, out.next_rays.data(),
+                            out.alive.data(), out.direct.data()));
+    return out;
+}
+
 inline void write_p6(const std::string& path, const Framebuffer& fb, const rt_ppm_options* opt = nullptr) {
     check(rt_ppm_write(path.c_str(), fb.rgb.data(), fb.width, fb.height, opt));
 }

@@ -29,6 +29,8 @@ RT_TIME_GATHER, RT_TIME_DELIVER, RT_TIME_FRAME = 0, 1, 2
 RT_FAULT_FRUSTUM_STACK = 1
 RT_RAYS_CLOSEST, RT_RAYS_OCCLUDED = 0, 1
 RT_RAYS_VARIANT_NONE, RT_RAYS_VARIANT_WIDE, RT_RAYS_VARIANT_BINARY, RT_RAYS_VARIANT_DEEP = 0, 1, 2, 3
+RT_PATH_LAST = 16
+RT_PATH_NONE = 0xFFFFFFFF
 # rt_tune_id (include/rt_mi355x.h): knob name -> id
 TUNE = {"frustum_arity": 0, "half_waves": 1, "paired_only": 2, "heavy_frac": 3, "heavy_cap": 4,
         "cull_coverage": 5, "cull_boxes": 6, "big_scene_bytes": 7, "frustum_stack_cap": 8,
@@ -115,6 +117,14 @@ class RenderOpts(C.Structure):
 
 class ShadeOpts(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("diffuse_bounce", C.c_int32), ("miss_color", Vec3), ("flags", C.c_int32)]
+
+
+class PathOpts(C.Structure):
+    _fields_ = [("diffuse_bounce", C.c_int32), ("miss_color", Vec3), ("flags", C.c_int32)]
+
+
+class PathStateT(C.Structure):
+    _fields_ = [("radiance", C.c_void_p), ("throughput", C.c_void_p), ("rng", C.c_void_p)]
 
 
 class Ray(C.Structure):
@@ -222,6 +232,14 @@ SIGNATURES = {
     "rt_film_resolve_device": (I, [P, I, I, P, P, P]),
     "rt_film_row_samples": (I, [P, I, P]),
     "rt_film_pixels_host": (I, [P, I, I, I, P, C.c_int64, P]),
+    "rt_path_opts_default": (None, [P]),
+    "rt_path_begin_device": (I, [I, SZ, P, P, P]),
+    "rt_path_step_device": (I, [P, SZ, P, P, P, P, P, P, P, P, P, P]),
+    "rt_path_step_variant": (I, [P]),
+    "rt_path_step_host": (I, [SZ, P, P, P, P, P, I, P, I, P, P, P, P, P, P]),
+    "rt_path_compact_scratch_bytes": (SZ, [SZ]),
+    "rt_path_compact_device": (I, [I, SZ, P, P, P, P, P, P, P, P]),
+    "rt_path_finish_device": (I, [I, SZ, P, P]),
     "rt_powf_host": (C.c_float, [C.c_float, C.c_float]),
     "rt_debug_frustum_records": (C.c_int, [C.c_size_t, P, P, C.c_int, C.c_int, P, P, C.c_size_t]),
     "rt_debug_scene_pack": (I, [SZ, P, P, P, P, P]),

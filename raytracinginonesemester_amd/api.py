@@ -479,7 +479,8 @@ class DeviceScene:
 
     def render_rays(self, camera: Camera, spp: int, max_depth: int = 1, diffuse_bounce: bool = True,
                     miss_color=(0, 0, 0), jitter=None, pass_spp: Optional[int] = None,
-                    band_rows: Optional[int] = None, ray_fn=None, p6: bool = False, film: Optional["Film"] = None):
+                    band_rows: Optional[int] = None, ray_fn=None, p6: bool = False, film: Optional["Film"] = None,
+                    material_fn=None):
         """A frame through the query path, on the device: for every sample pass (``pass_spp``
         samples; default all) and row band (``band_rows`` rows; default all) camera_rays ->
         ``ray_fn`` -> shade_rays -> Film.add, then one Film.resolve.  Memory is bounded by one
@@ -491,6 +492,8 @@ class DeviceScene:
         ``jitter``: (spp, 2) float32, None for jittered_samples(spp).  ``film``: a Film of the
         camera's size to accumulate into (neither cleared before nor closed after: samples already
         there stay in the sums); default a new one, closed on return.
+        ``material_fn``: when given, the step's radiance comes from trace_paths with that hook (a
+        material per hit; see trace_paths) instead of shade_rays.
         Returns Film.resolve's result for the whole image, on torch's current stream."""
         W, H, spp = camera.pixel_width, camera.pixel_height, int(spp)
         if spp < 1:
@@ -515,7 +518,10 @@ class DeviceScene:
                     rays, seeds = camera_rays(camera, n, jit[s0:s0 + n], r0, rows, device=self.device, sample0=s0)
                     if ray_fn is not None:
                         rays = ray_fn(rays, seeds, r0, rows, s0, n)
-                    rad = self.shade_rays(rays, seeds, max_depth, diffuse_bounce, miss_color)
+                    if material_fn is None:
+                        rad = self.shade_rays(rays, seeds, max_depth, diffuse_bounce, miss_color)
+                    else:
+                        rad = self.trace_paths(rays, seeds, max_depth, diffuse_bounce, miss_color, material_fn=material_fn)
                     film.add(rad, r0, rows, n)
             return film.resolve(p6=p6)
         finally:
@@ -561,6 +567,124 @@ class DeviceScene:
     def trace_hits_variant(self) -> int:
         """The traversal the latest trace_hits call launched (RT_RAYS_VARIANT_*)."""
         return int(lib().rt_trace_hits_variant(self._handle()))
+
+    # ---- path stages for caller hits (rt_path_*) ------------------------------------------------
+    def _torch_dev(self):
+        import torch
+
+        return torch.device("cuda", self.device)
+
+    def path_begin(self, n: int, seeds=None, stream: Optional[int] = None) -> "PathState":
+        """The state of ``n`` paths at the top of TraceRayIterative (rt_path_begin_device): radiance
+        0, throughput 1, rng ``seeds`` (n uint32 as an int32 / uint32 tensor or an array; None: 42).
+        One launch on ``stream`` (default torch's current stream)."""
+        import torch
+
+        dev, n = self._torch_dev(), int(n)
+        sd = _seed_tensor(seeds, n, dev, "path_begin")
+        st = PathState(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev),
+                       torch.empty(n, dtype=torch.int32, device=dev))
+        if n > 0:
+            check(lib().rt_path_begin_device(self.device, n, None if sd is None else sd.data_ptr(), C.byref(st.c),
+                                             _stream_of(stream, dev)))
+        return st
+
+    def path_step(self, rays, hits, state: "PathState", ids=None, materials=None, diffuse_bounce: bool = True,
+                  miss_color=(0, 0, 0), flags: int = 0, last: bool = False, direct: bool = False, next_rays=None,
+                  stream: Optional[int] = None):
+        """One depth of TraceRayIterative's loop for ``m`` entries (rt_path_step_device): ``rays``
+        (m, 6) float32 and ``hits`` (m, 16) int32, trace_hits' records or the caller's edits of
+        them (tri, p, normal and material are read); entry k updates path ``ids[k]`` (int32 tensor,
+        unique; None: k; -1: no path) of ``state``.  ``materials``: (m, 13) float32, a material per
+        hit, or None for the scene's table entry of the record.  A miss adds throughput *
+        ``miss_color``; a hit adds the direct lighting with shadow rays and, unless ``last``, makes
+        the bounce.
+
+        Returns ``(next_rays, alive)`` [``, direct`` with ``direct=True``: ShadeDirect's value per
+        entry, (m, 3)]: alive (m,) uint8 is 1 where the path goes on with next_rays[k]; a dead entry
+        keeps its input ray.  ``next_rays`` may name the output tensor, ``rays`` itself included.
+        With ``last`` (a path's last depth) there is no bounce and no draw, and (None, None) is
+        returned unless ``next_rays`` is given.  ``flags``: RT_FLAG_BINARY or 0."""
+        import torch
+
+        dev = self._torch_dev()
+        if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6 or not rays.is_contiguous():
+            raise ValueError(f"path_step: rays must be a contiguous (m, 6) float32 tensor on {dev}")
+        m = rays.shape[0]
+        if hits.device != dev or hits.dtype != torch.int32 or tuple(hits.shape) != (m, 16) or not hits.is_contiguous():
+            raise ValueError("path_step: hits must be the contiguous (m, 16) int32 tensor of trace_hits")
+        if ids is not None and (ids.device != dev or ids.dtype != torch.int32 or tuple(ids.shape) != (m,) or not ids.is_contiguous()):
+            raise ValueError("path_step: ids must be a contiguous (m,) int32 tensor")
+        if ids is None and m > state.n:
+            raise ValueError("path_step: more entries than paths in the state")
+        if materials is not None and (materials.device != dev or materials.dtype != torch.float32
+                                      or tuple(materials.shape) != (m, 13) or not materials.is_contiguous()):
+            raise ValueError("path_step: materials must be a contiguous (m, 13) float32 tensor")
+        if next_rays is not None and (next_rays.device != dev or next_rays.dtype != torch.float32
+                                      or tuple(next_rays.shape) != (m, 6) or not next_rays.is_contiguous()):
+            raise ValueError("path_step: next_rays must be a contiguous (m, 6) float32 tensor")
+        want_out = not last or next_rays is not None
+        if want_out and next_rays is None:
+            next_rays = torch.empty((m, 6), dtype=torch.float32, device=dev)
+        alive = torch.empty(m, dtype=torch.uint8, device=dev) if want_out else None
+        d = torch.empty((m, 3), dtype=torch.float32, device=dev) if direct else None
+        if m > 0:
+            o = L.PathOpts(1 if diffuse_bounce else 0, _v3(miss_color), int(flags) | (L.RT_PATH_LAST if last else 0))
+            check(lib().rt_path_step_device(self._handle(), m, rays.data_ptr(), hits.data_ptr(),
+                                            None if materials is None else materials.data_ptr(),
+                                            None if ids is None else ids.data_ptr(), C.byref(o), C.byref(state.c),
+                                            None if next_rays is None else next_rays.data_ptr(),
+                                            None if alive is None else alive.data_ptr(), None if d is None else d.data_ptr(),
+                                            _stream_of(stream, dev)))
+        return (next_rays, alive, d) if direct else (next_rays, alive)
+
+    def path_step_variant(self) -> int:
+        """The traversal the latest path_step call launched for its shadow rays (RT_RAYS_VARIANT_*)."""
+        return int(lib().rt_path_step_variant(self._handle()))
+
+    def trace_paths(self, rays, seeds=None, max_depth: int = 1, diffuse_bounce: bool = True, miss_color=(0, 0, 0),
+                    material_fn=None, compact: bool = True, flags: int = 0):
+        """Radiance of caller rays by stages, on torch's current stream: path_begin, then per depth
+        trace_hits -> ``material_fn`` -> path_step -> compact_paths, then path_finish.  With
+        ``material_fn=None`` the result is shade_rays' bit for bit.
+
+        ``material_fn(hits, rays, ids, depth)`` gets the depth's records ((m, 16) int32, hit_fields
+        names them; it may edit them in place), rays and path ids ((m,) int32; -1: an ended path,
+        only without ``compact``) and returns an (m, 13) float32 tensor, a material per hit, or None
+        for the scene's table.  ``compact``: the live rays are packed after every depth (one read
+        of their count, the one synchronisation per depth); without it every depth runs all n
+        entries, the ended ones as no path.  The last depth's step is issued with RT_PATH_LAST;
+        ``max_depth <= 0`` returns zeros without a launch.  Returns (n, 3) float32, clamped."""
+        import torch
+
+        dev = self._torch_dev()
+        if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError(f"trace_paths: expects an (n, 6) float32 tensor on {dev}")
+        n = rays.shape[0]
+        if int(max_depth) <= 0 or n == 0:
+            return torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        state = self.path_begin(n, seeds)
+        cur, ids = rays.contiguous(), None
+        for depth in range(int(max_depth)):
+            last = depth + 1 == int(max_depth)
+            hits = self.trace_hits(cur, flags)
+            mats = None
+            if material_fn is not None:
+                shown = ids if ids is not None else torch.arange(n, dtype=torch.int32, device=dev)
+                mats = material_fn(hits, cur, shown, depth)
+                if mats is not None:
+                    mats = mats.to(dtype=torch.float32).contiguous()
+            nxt, alive = self.path_step(cur, hits, state, ids, mats, diffuse_bounce, miss_color, flags, last=last)
+            if last:
+                break
+            if compact:
+                cur, ids, count = compact_paths(alive, nxt, ids)
+                if count == 0:
+                    break
+            else:
+                own = ids if ids is not None else torch.arange(n, dtype=torch.int32, device=dev)
+                cur, ids = nxt, torch.where(alive != 0, own, torch.full_like(own, -1))
+        return path_finish(state)
 
     def faults(self, clear: bool = True) -> int:
         """RT_FAULT_* bits the device guards raised since the last clear (rt_scene_faults)."""
@@ -1044,6 +1168,118 @@ class Film:
             self.close()
         except Exception:
             pass
+
+
+def _stream_of(stream, dev):
+    import torch
+
+    return torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+
+
+def _seed_tensor(seeds, n: int, dev, who: str):
+    """n uint32 seeds as an int32 tensor on dev (the same 32 bits), or None."""
+    import torch
+
+    if seeds is None:
+        return None
+    if type(seeds).__module__.split(".")[0] == "torch":
+        if seeds.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or seeds.device != dev:
+            raise ValueError(f"{who}: seeds must be an int32 or uint32 tensor on {dev}")
+        sd = seeds.contiguous()
+    else:
+        sd = torch.from_numpy(_c(seeds, np.uint32).view(np.int32)).to(dev)
+    if tuple(sd.shape) != (n,):
+        raise ValueError(f"{who}: seeds must hold one uint32 per path")
+    return sd
+
+
+class PathState:
+    """The state of n staged paths on a device (rt_path_state): ``radiance`` (n, 3) float32,
+    ``throughput`` (n, 3) float32 and ``rng`` (n,) int32 (the rng's 32 bits), indexed by path id.
+    DeviceScene.path_begin makes one; path_step updates it; path_finish clamps its radiance."""
+
+    def __init__(self, radiance, throughput, rng):
+        self.radiance, self.throughput, self.rng = radiance, throughput, rng
+        self.n = int(rng.shape[0])
+        self.c = L.PathStateT(radiance.data_ptr(), throughput.data_ptr(), rng.data_ptr())
+
+
+def path_finish(state: PathState, stream: Optional[int] = None):
+    """The reference's final clamp on every path's radiance, in place (rt_path_finish_device);
+    returns ``state.radiance``."""
+    dev = state.radiance.device
+    if state.n > 0:
+        check(lib().rt_path_finish_device(dev.index, state.n, state.radiance.data_ptr(), _stream_of(stream, dev)))
+    return state.radiance
+
+
+def compact_paths(alive, rays, ids=None, stream: Optional[int] = None):
+    """Stable compaction of a step's live rays (rt_path_compact_device): for the k with
+    ``alive[k] != 0``, in increasing k, ``rays[k]`` and its path id (``ids[k]``; None: k).
+    ``alive`` (m,) uint8, ``rays`` (m, 6) float32, ``ids`` (m,) int32, on one device.  Returns
+    ``(rays, ids, count)``, the first ``count`` rows of new tensors; count is read back, which
+    waits for the stream."""
+    import torch
+
+    dev = rays.device
+    m = rays.shape[0]
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6 or not rays.is_contiguous():
+        raise ValueError("compact_paths: rays must be a contiguous (m, 6) float32 tensor")
+    if alive.device != dev or alive.dtype != torch.uint8 or tuple(alive.shape) != (m,) or not alive.is_contiguous():
+        raise ValueError("compact_paths: alive must be a contiguous (m,) uint8 tensor on the rays' device")
+    if ids is not None and (ids.device != dev or ids.dtype != torch.int32 or tuple(ids.shape) != (m,) or not ids.is_contiguous()):
+        raise ValueError("compact_paths: ids must be a contiguous (m,) int32 tensor on the rays' device")
+    out_r = torch.empty((m, 6), dtype=torch.float32, device=dev)
+    out_i = torch.empty(m, dtype=torch.int32, device=dev)
+    if m == 0:
+        return out_r, out_i, 0
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(max(int(lib().rt_path_compact_scratch_bytes(m)) // 4, 1), dtype=torch.int32, device=dev)
+    cur = torch.cuda.current_stream(dev)
+    st = _stream_of(stream, dev)
+    check(lib().rt_path_compact_device(dev.index, m, alive.data_ptr(), rays.data_ptr(), None if ids is None else ids.data_ptr(),
+                                       out_r.data_ptr(), out_i.data_ptr(), count.data_ptr(), scratch.data_ptr(), st))
+    if st != cur.cuda_stream:
+        torch.cuda.ExternalStream(st, device=dev).synchronize()
+    c = int(count.item())
+    return out_r[:c], out_i[:c], c
+
+
+def path_step_host(rays, hits, radiance, throughput, rng, occluded, lights, table=None, materials=None, ids=None,
+                   diffuse_bounce: bool = True, miss_color=(0, 0, 0), last: bool = False):
+    """Host build of the step's arithmetic (rt_path_step_host, no device): numpy arrays in
+    path_step's shapes (``hits`` (m,) HIT_DTYPE, ``lights`` LIGHT_DTYPE, ``table`` (nm, 13) or None),
+    the state arrays ``radiance``, ``throughput`` (N, 3) float32 and ``rng`` (N,) uint32 updated in
+    place, and ``occluded`` (m, num_lights) uint8, read where the kernel would cast entry k's shadow
+    ray to light l.  Returns ``(next_rays, alive, direct)``."""
+    r = _c(rays, np.float32)
+    m = r.shape[0]
+    h = np.ascontiguousarray(hits, HIT_DTYPE)
+    lt = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    occ = _c(occluded, np.uint8).reshape(m, lt.size)
+    tb = None if table is None else _c(table, np.float32).reshape(-1, 13)
+    mt = None if materials is None else _c(materials, np.float32)
+    idv = None if ids is None else _c(ids, np.uint32)
+    for a, dt in ((radiance, np.float32), (throughput, np.float32), (rng, np.uint32)):
+        if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError("path_step_host: the state must be writeable contiguous float32 / uint32 arrays")
+    N = rng.shape[0]
+    if r.shape != (m, 6) or h.shape != (m,) or radiance.shape != (N, 3) or throughput.shape != (N, 3) \
+            or (mt is not None and mt.shape != (m, 13)) or (idv is not None and idv.shape != (m,)):
+        raise ValueError("path_step_host: the arrays do not match the batch")
+    used = idv[idv != L.RT_PATH_NONE] if idv is not None else np.arange(m)
+    if used.size and int(used.max()) >= N:
+        raise ValueError("path_step_host: a path id outside the state")
+    nxt = np.zeros((m, 6), np.float32)
+    alive = np.zeros(m, np.uint8)
+    direct = np.zeros((m, 3), np.float32)
+    st = L.PathStateT(ptr(radiance), ptr(throughput), ptr(rng))
+    o = L.PathOpts(1 if diffuse_bounce else 0, _v3(miss_color), L.RT_PATH_LAST if last else 0)
+    if m > 0:
+        check(lib().rt_path_step_host(m, ptr(r), ptr(h), ptr(mt), ptr(idv), ptr(tb) if tb is not None and tb.size else None,
+                                      0 if tb is None else tb.shape[0], ptr(lt) if lt.size else None, lt.size,
+                                      ptr(occ) if occ.size else None, C.byref(o), C.byref(st), ptr(nxt), ptr(alive), ptr(direct)))
+    return nxt, alive, direct
 
 
 def film_pixels_host(radiance, width: int, rows: int, nsamples: int, sums=None, count_after: Optional[int] = None):

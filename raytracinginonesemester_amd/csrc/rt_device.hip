@@ -35,6 +35,7 @@
 //   rt_shade.hpp       hit resolution, materials, camera ray, shading, bounces, trace_sample
 //   rt_prepass.hpp     tile bounds, root and tree-cut culling passes, work lists
 //   rt_query.hpp       batched ray queries on a resident scene (rt_trace_rays*, rt_shade_rays*)
+//   rt_path.hpp        path stages for caller hits (rt_path_*): step, begin, compaction, finish
 // Separate translation units: rt_scene_pack.cpp (the host half of rt_scene_create: checks, ids,
 // stack bounds, every packed array), rt_records.cpp (host record builders), rt_hw1.hip (the HW1
 // path), rt_frame.hip, rt_lbvh.hip, rt_renderer.hip.
@@ -191,6 +192,7 @@ struct RenderParams {
 #include "rt_shade.hpp"
 #include "rt_prepass.hpp"
 #include "rt_query.hpp"
+#include "rt_path.hpp"
 
 // The render kernel's work: list q's entries, its heavy lists' first (classes in order,
 // heaviest first; each capped at heavy_cap), then its survivors (the cut pass's list, or the
@@ -664,6 +666,8 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     std::atomic<int> shade_variant{RT_RAYS_VARIANT_NONE};
     // ... and of the latest rt_trace_hits[_device] call
     std::atomic<int> hits_variant{RT_RAYS_VARIANT_NONE};
+    // ... and of the latest rt_path_step_device call
+    std::atomic<int> path_variant{RT_RAYS_VARIANT_NONE};
     DevBuf inode, wnode, ibox, leaf, tnorm, objids, mats, lights, jitter;
     DevBuf fnode;    // 2^f_log2-ary records of the frustum traversal (empty: it takes wnode's 4-ary ones)
     DevBuf qent, qhdr;  // fnode quantised (build_quant_records): the big-scene kernels' records
@@ -1966,6 +1970,233 @@ extern "C" int rt_camera_rays_pass_device(int device, const rt_camera* cam, int 
 extern "C" int rt_camera_rays_device(int device, const rt_camera* cam, int spp, const float* jitter, int row0, int rows,
                                      rt_ray* rays, uint32_t* seeds, void* stream) {
     return rt_camera_rays_pass_device(device, cam, 0, spp, jitter, row0, rows, rays, seeds, stream);
+}
+
+// ---- path stages (rt_path.hpp) -------------------------------------------------------------------
+static_assert(sizeof(DevMaterial) == sizeof(rt_material) && sizeof(DevLight) == sizeof(rt_light), "reference layouts");
+static_assert(PATH_NONE == RT_PATH_NONE, "RT_PATH_NONE");
+
+extern "C" void rt_path_opts_default(rt_path_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->diffuse_bounce = 1;
+}
+
+namespace {
+// The checks the device and the host form of the step share: no HIP call and no read through any
+// pointer but opt and st before they pass.
+int path_step_args(const char* who, size_t m, const void* rays, const void* hits, const rt_path_opts* opt,
+                   const rt_path_state* st, const void* next, const void* alive, int known_flags) {
+    if (!opt) return set_error(RT_ERR_ARG, std::string(who) + ": null opts");
+    if (opt->flags & ~known_flags) return set_error(RT_ERR_ARG, std::string(who) + ": unknown flag");
+    if (m > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31-1 entries in one batch");
+    if (!rays || !hits) return set_error(RT_ERR_ARG, std::string(who) + ": null rays or hits");
+    if (!st || !st->radiance || !st->throughput || !st->rng) return set_error(RT_ERR_ARG, std::string(who) + ": null state");
+    if (!(opt->flags & RT_PATH_LAST) && (!next || !alive))
+        return set_error(RT_ERR_ARG, std::string(who) + ": next_rays and alive are required unless RT_PATH_LAST is set");
+    return RT_OK;
+}
+
+int path_state_args(const char* who, size_t n, const rt_path_state* st) {
+    if (!st || !st->radiance || !st->throughput || !st->rng) return set_error(RT_ERR_ARG, std::string(who) + ": null state");
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31-1 paths");
+    return RT_OK;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && na && nb && x < y + nb && y < x + na;
+}
+
+// Tiles of n entries, and the scratch words of a scan over n entries that recurses through them.
+size_t path_tiles(size_t n) { return (n + PATH_TILE - 1) / PATH_TILE; }
+size_t path_scan_words(size_t n) {
+    size_t words = 0;
+    while (n > PATH_TILE) {
+        n = path_tiles(n);
+        words += n;
+    }
+    return words;
+}
+
+// a[0..n) to exclusive prefix sums in place, the sum to *total: one launch for one tile, else the
+// tiles' sums (the next words of scratch), their scan, and the tiles' scans from those offsets.
+void path_scan(uint32_t* a, size_t n, uint32_t* scratch, uint32_t* total, hipStream_t st) {
+    if (n <= PATH_TILE) {
+        hipLaunchKernelGGL(path_scan_kernel, dim3(1), dim3(BLOCK), 0, st, a, uint32_t(n), nullptr, total);
+        return;
+    }
+    const size_t nt = path_tiles(n);
+    hipLaunchKernelGGL(path_tile_sums_kernel, dim3(unsigned(nt)), dim3(BLOCK), 0, st, a, uint32_t(n), scratch);
+    path_scan(scratch, nt, scratch + nt, total, st);
+    hipLaunchKernelGGL(path_scan_kernel, dim3(unsigned(nt)), dim3(BLOCK), 0, st, a, uint32_t(n), scratch, nullptr);
+}
+}  // namespace
+
+extern "C" int rt_path_begin_device(int device, size_t n, const uint32_t* seeds, const rt_path_state* state, void* stream) {
+    int rc = path_state_args("rt_path_begin_device", n, state);
+    if (rc != RT_OK || n == 0) return rc;
+    if ((rc = check_device(device)) != RT_OK) return rc;
+    DeviceGuard g(device);
+    PathBeginParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.seeds = seeds;
+    P.n = uint32_t(n);
+    P.radiance = state->radiance;
+    P.throughput = state->throughput;
+    P.rng = state->rng;
+    hipLaunchKernelGGL(path_begin_kernel, dim3((P.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" int rt_path_finish_device(int device, size_t n, float* radiance, void* stream) {
+    if (!radiance) return set_error(RT_ERR_ARG, "rt_path_finish_device: null radiance");
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_path_finish_device: more than 2^31-1 paths");
+    if (n == 0) return RT_OK;
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    DeviceGuard g(device);
+    hipLaunchKernelGGL(path_finish_kernel, dim3((uint32_t(n) + BLOCK - 1) / BLOCK), dim3(BLOCK), 0,
+                       static_cast<hipStream_t>(stream), radiance, uint32_t(n));
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" int rt_path_step_device(rt_scene* s, size_t m, const rt_ray* rays, const rt_hit* hits, const rt_material* mats,
+                                   const uint32_t* ids, const rt_path_opts* opt, const rt_path_state* state, rt_ray* next,
+                                   uint8_t* alive, float* direct, void* stream) {
+    if (!s) return set_error(RT_ERR_ARG, "rt_path_step_device: null scene");
+    const int rc = path_step_args("rt_path_step_device", m, rays, hits, opt, state, next, alive, RT_FLAG_BINARY | RT_PATH_LAST);
+    if (rc != RT_OK) return rc;
+    // the kernel loads 16-byte words
+    if (reinterpret_cast<uintptr_t>(hits) % 16 != 0) return set_error(RT_ERR_ARG, "rt_path_step_device: hits_dev is not 16-byte aligned");
+    if (m == 0) return RT_OK;
+    DeviceGuard g(s->device);
+    // trace_rays_launch's variant rule; of the scene the step writes path_variant alone
+    int variant = RT_RAYS_VARIANT_DEEP;
+    if (!s->deep) {
+        if (s->wide && s->lane_wide && !(opt->flags & RT_FLAG_BINARY)) variant = RT_RAYS_VARIANT_WIDE;
+        else if (s->lane_stack) variant = RT_RAYS_VARIANT_BINARY;
+    }
+    if (s->deep && !s->tri.p) return set_error(RT_ERR_INTERNAL, "rt_path_step_device: a deep scene without its triangle array");
+    PathStepParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.sc = scene_view(s);  // (the packed records of the shadow rays and the shading tables)
+    P.sc.wide = variant == RT_RAYS_VARIANT_WIDE ? 1 : 0;
+    P.sc.f_log2 = 2;
+    P.sc.ncut = 0;
+    P.rays = reinterpret_cast<const float*>(rays);
+    P.hits = reinterpret_cast<const uint4*>(hits);
+    P.mats = reinterpret_cast<const float*>(mats);
+    P.ids = ids;
+    P.m = uint32_t(m);
+    P.diffuse_bounce = opt->diffuse_bounce;
+    P.last = (opt->flags & RT_PATH_LAST) ? 1 : 0;
+    P.miss = mk(opt->miss_color.x, opt->miss_color.y, opt->miss_color.z);
+    P.radiance = state->radiance;
+    P.throughput = state->throughput;
+    P.rng = state->rng;
+    P.next = P.last && !next ? nullptr : reinterpret_cast<float*>(next);
+    P.alive = alive;
+    P.direct = direct;
+    const dim3 grid((P.m + BLOCK - 1) / BLOCK), block(BLOCK);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (variant == RT_RAYS_VARIANT_WIDE) hipLaunchKernelGGL((path_step_kernel<RT_RAYS_VARIANT_WIDE>), grid, block, 0, st, P);
+    else if (variant == RT_RAYS_VARIANT_BINARY) hipLaunchKernelGGL((path_step_kernel<RT_RAYS_VARIANT_BINARY>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((path_step_kernel<RT_RAYS_VARIANT_DEEP>), grid, block, 0, st, P);
+    HIP_TRY(hipGetLastError());
+    s->path_variant.store(variant, std::memory_order_relaxed);
+    return RT_OK;
+}
+
+extern "C" int rt_path_step_variant(const rt_scene* s) {
+    return s ? s->path_variant.load(std::memory_order_relaxed) : RT_RAYS_VARIANT_NONE;
+}
+
+// The host build of the step: path_step_one as path_step_kernel runs it, the shadow rays' answers
+// read from `occluded`.
+extern "C" int rt_path_step_host(size_t m, const rt_ray* rays, const rt_hit* hits, const rt_material* mats,
+                                 const uint32_t* ids, const rt_material* table, int num_table, const rt_light* lights,
+                                 int num_lights, const uint8_t* occluded, const rt_path_opts* opt, const rt_path_state* state,
+                                 rt_ray* next, uint8_t* alive, float* direct) {
+    const int rc = path_step_args("rt_path_step_host", m, rays, hits, opt, state, next, alive, RT_FLAG_BINARY | RT_PATH_LAST);
+    if (rc != RT_OK) return rc;
+    if (num_table < 0 || num_lights < 0 || (num_table > 0 && !table) || (num_lights > 0 && (!lights || !occluded)))
+        return set_error(RT_ERR_ARG, "rt_path_step_host: a table, light set or occlusion array that does not match its count");
+    const bool last = (opt->flags & RT_PATH_LAST) != 0;
+    const f3 miss = mk(opt->miss_color.x, opt->miss_color.y, opt->miss_color.z);
+    for (size_t k = 0; k < m; ++k) {
+        const float* R = reinterpret_cast<const float*>(rays + k);
+        float* nx = next ? reinterpret_cast<float*>(next + k) : nullptr;
+        const uint32_t id = ids ? ids[k] : uint32_t(k);
+        if (id == PATH_NONE) {
+            if (nx) std::memmove(nx, R, sizeof(rt_ray));
+            if (alive) alive[k] = 0;
+            if (direct) direct[3 * k] = direct[3 * k + 1] = direct[3 * k + 2] = 0.0f;
+            continue;
+        }
+        HitWords h;  // (the caller's records need no alignment)
+        std::memcpy(&h, hits + k, sizeof(h));
+        path_step_one(R, h.w, mats ? reinterpret_cast<const float*>(mats + k) : nullptr,
+                      reinterpret_cast<const DevMaterial*>(table), num_table, reinterpret_cast<const DevLight*>(lights),
+                      num_lights, miss, opt->diffuse_bounce != 0, last, state->radiance + 3 * size_t(id),
+                      state->throughput + 3 * size_t(id), state->rng + id, nx, alive ? alive + k : nullptr,
+                      direct ? direct + 3 * k : nullptr,
+                      [&](int li, f3, f3, float) { return occluded[k * size_t(num_lights) + size_t(li)] != 0; });
+    }
+    return RT_OK;
+}
+
+extern "C" size_t rt_path_compact_scratch_bytes(size_t m) {
+    if (m == 0 || m > 0x7FFFFFFFull) return 0;
+    const size_t nt = path_tiles(m);
+    return sizeof(uint32_t) * (nt + path_scan_words(nt));
+}
+
+extern "C" int rt_path_compact_device(int device, size_t m, const uint8_t* alive, const rt_ray* rays_in, const uint32_t* ids_in,
+                                      rt_ray* rays_out, uint32_t* ids_out, uint32_t* count, void* scratch, void* stream) {
+    if (m > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_path_compact_device: more than 2^31-1 entries in one batch");
+    if (!count) return set_error(RT_ERR_ARG, "rt_path_compact_device: null count");
+    if (m > 0) {
+        if (!alive || !rays_in || !rays_out || !ids_out || !scratch)
+            return set_error(RT_ERR_ARG, "rt_path_compact_device: null alive, rays, ids_out or scratch");
+        if (reinterpret_cast<uintptr_t>(scratch) % 4 != 0) return set_error(RT_ERR_ARG, "rt_path_compact_device: scratch_dev is not 4-byte aligned");
+        const size_t rb = m * sizeof(rt_ray), ib = m * sizeof(uint32_t), sb = rt_path_compact_scratch_bytes(m);
+        const struct { const void* p; size_t n; } in[3] = {{alive, m}, {rays_in, rb}, {ids_in, ib}},
+                                                  out[4] = {{rays_out, rb}, {ids_out, ib}, {count, sizeof(uint32_t)}, {scratch, sb}};
+        for (const auto& o : out)
+            for (const auto& i : in)
+                if (ranges_overlap(o.p, o.n, i.p, i.n)) return set_error(RT_ERR_ARG, "rt_path_compact_device: an output overlaps an input");
+        for (int a = 0; a < 4; ++a)
+            for (int b = a + 1; b < 4; ++b)
+                if (ranges_overlap(out[a].p, out[a].n, out[b].p, out[b].n))
+                    return set_error(RT_ERR_ARG, "rt_path_compact_device: two outputs overlap");
+    }
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    DeviceGuard g(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m == 0) {
+        HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), st));
+        return RT_OK;
+    }
+    const size_t nt = path_tiles(m);
+    uint32_t* counts = static_cast<uint32_t*>(scratch);
+    hipLaunchKernelGGL(path_count_kernel, dim3(unsigned(nt)), dim3(BLOCK), 0, st, alive, uint32_t(m), counts);
+    path_scan(counts, nt, counts + nt, count, st);
+    PathScatterParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.alive = alive;
+    P.m = uint32_t(m);
+    P.offsets = counts;
+    P.rays_in = reinterpret_cast<const float*>(rays_in);
+    P.ids_in = ids_in;
+    P.rays_out = reinterpret_cast<float*>(rays_out);
+    P.ids_out = ids_out;
+    hipLaunchKernelGGL(path_scatter_kernel, dim3(unsigned(nt)), dim3(BLOCK), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 void rt::scene_set_caller_ordered(rt_scene* s, bool on) {

@@ -51,8 +51,8 @@ __device__ __forceinline__ DevMaterial material_of(const SceneView& sc, int32_t 
     return m;
 }
 
-// EvaluateBRDF (brdf.h:12-40)
-__device__ __forceinline__ f3 eval_brdf(const DevMaterial& m, f3 N, f3 V, f3 L) {
+// EvaluateBRDF (brdf.h:12-40); the host build serves rt_path_step_host (rt_path.hpp)
+__host__ __device__ __forceinline__ f3 eval_brdf(const DevMaterial& m, f3 N, f3 V, f3 L) {
     const float NdotL = fmaxf(dot(N, L), 0.0f);
     const float NdotV = fmaxf(dot(N, V), 0.0f);
     if (NdotL <= 0.f || NdotV <= 0.f) return mk(0.f, 0.f, 0.f);
