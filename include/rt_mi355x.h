@@ -40,7 +40,11 @@ extern "C" {
                                  RT_PATH_NONE, rt_path_opts_default, rt_path_begin_device,
                                  rt_path_step_device, rt_path_step_variant, rt_path_step_host,
                                  rt_path_compact_scratch_bytes, rt_path_compact_device,
-                                 rt_path_finish_device */
+                                 rt_path_finish_device; RT_PIXEL_NONE, rt_camera_rays_pixels_host,
+                                 rt_camera_rays_pixels_device, rt_afilm, rt_afilm_select_opts,
+                                 rt_afilm_create, rt_afilm_destroy, rt_afilm_clear_device,
+                                 rt_afilm_counts_device, rt_afilm_add_device, rt_afilm_resolve_device,
+                                 rt_afilm_select_scratch_bytes, rt_afilm_select_device, rt_afilm_host */
 
 enum {
     RT_OK = 0,
@@ -778,6 +782,93 @@ int rt_path_compact_device(int device, size_t m, const uint8_t* alive_dev, const
                            const uint32_t* ids_in_dev, rt_ray* rays_out_dev, uint32_t* ids_out_dev,
                            uint32_t* count_dev, void* scratch_dev, void* hip_stream);
 int rt_path_finish_device(int device, size_t n, float* radiance_dev, void* hip_stream);
+
+/* ---- adaptive sampling: per-pixel sample counts, pixel-list rays and film ----------------------
+ * Spending samples unevenly, exactly.  jittered_samples(k, 42) is a prefix of
+ * jittered_samples(n, 42) for k <= n (one mt19937 stream), make_rng_seed(x, y, s) does not read
+ * spp, and render() sums in sample order and divides by float(spp): a pixel that has received
+ * samples 0..c-1 in order and is resolved with its own count c is render()'s pixel at spp = c, bit
+ * for bit.  A pass is  select -> rt_camera_rays_pixels_device -> rt_shade_rays_device (or the path
+ * stages) -> rt_afilm_add_device,  all on the device; the only thing a host needs per pass is the
+ * number of selected pixels.
+ * Conventions as for rt_film_* and rt_path_*: device pointers on the object's device, one or a
+ * few launches per call on the caller's hip_stream (NULL = the null stream), asynchronous, no host
+ * synchronisation, every argument check before any HIP call, no block waits for another, one
+ * writer per word (plain stores, no atomics).  Results are specified for finite radiance.
+ *
+ * rt_camera_rays_pixels_*: camera rays for a list of pixels.  pixels: m indices y * W + x in any
+ *   order; NULL means entry k is pixel k, and m must then be W * H.  counts: W * H words, the
+ *   samples each pixel already has (rt_afilm_counts_device); NULL means 0 for all.  Ray
+ *   k * nsamples + s is sample counts[pixels[k]] + s of that pixel: Camera::get_ray with that
+ *   entry of jitter (the whole frame's table, table_spp entries of (jx, jy); on the host NULL
+ *   means rt_jittered_samples(table_spp, 42, 1)), the arithmetic of rt_camera_rays_pass_*; its seed
+ *   is make_rng_seed(x, y, counts + s); seeds may be NULL.  Memory-safe for any input: an index
+ *   >= W * H (RT_PIXEL_NONE is the marker) writes origin = center, direction 0 and seed 0; a sample
+ *   index >= table_spp reads the table's last entry and its result is unspecified.
+ *   m * nsamples > 2^31-1 (or W * H > 2^31-1) is RT_ERR_UNSUPPORTED; m == 0 is RT_OK with no launch;
+ *   a null camera, rays or (on the device) jitter, nsamples < 1 or table_spp < 1 is RT_ERR_ARG.
+ *
+ * rt_afilm: per pixel three float sums (rt_film's), a uint32 sample count and two float moments of
+ *   the sample luminance y = (0.2126f * r + 0.7152f * g) + 0.0722f * b (float multiplies and adds in
+ *   that order): m1 = sum of y, m2 = sum of y * y, accumulated in sample order like the sums.
+ *   24 bytes per pixel, all on the device: there are no host-side counts.
+ * rt_afilm_add_device: radiance_dev holds m * nsamples * 3 floats in the ray generator's order; for
+ *   entry k the samples go onto pixel pixels_dev[k]'s sums and moments in order and its count
+ *   grows by nsamples.  pixels_dev NULL: the dense add, m == W * H.  Indices must be unique within
+ *   a call (the caller's to keep); an index >= W * H is skipped.  Any alignment of radiance_dev; a
+ *   16-byte aligned pointer takes the faster kernel.  m * nsamples > 2^31-1 is RT_ERR_UNSUPPORTED,
+ *   m == 0 is RT_OK with no launch.
+ * rt_afilm_resolve_device: for rows [row0, row0 + rows): rgb_dev (rows*W*3 floats), each pixel
+ *   float(double(sum) / double(float(count))) with its own count; p6_dev (rows*W*3 bytes, write_p6's
+ *   defaults as rt_film_resolve_device writes them); counts_out_dev (rows*W words), the sample-count
+ *   map.  Any two of the three may be NULL.  A pixel with count 0 resolves to 0.0f, byte 0.  Does
+ *   not clear.
+ * rt_afilm_select_device: the indices of the pixels to sample next, in increasing order (a stable
+ *   compaction: per-tile counts, a scan, a scatter, in stream order), to pixels_out_dev (room for
+ *   W * H words) and their number to *count_dev.  scratch_dev: rt_afilm_select_scratch_bytes(f)
+ *   bytes, 4-byte aligned.  opts: min_samples >= 2, step >= 1, tol >= 0, floor > 0, else RT_ERR_ARG.
+ *   A pixel with count n is selected iff n + step <= max_samples and (n < min_samples or noisy(n)).
+ *   noisy is computed in double from the float accumulators with + - * /, max and comparisons only:
+ *     mean = m1 / n;  var = (max(0, m2 / n - mean * mean) * n) / (n - 1);
+ *     noisy iff var / n > (tol * max(mean, floor))^2;  n < 2 counts as noisy.
+ * rt_afilm_host: the host build of add, resolve and select over host arrays (no device needed),
+ *   through the functions the kernels run.  sum (W*H*3), count (W*H) and moments (W*H*2) are the
+ *   film's state, updated in place.  In this order: when radiance is not NULL, the add of m entries
+ *   (pixels NULL: dense); when rgb_out or p6_out is not NULL, the resolve of the whole image; when
+ *   opts is not NULL, the selection to pixels_out (W*H words) and *selected_out.  Same argument
+ *   rules. */
+#define RT_PIXEL_NONE 0xFFFFFFFFu
+int rt_camera_rays_pixels_host(const rt_camera* cam, const uint32_t* pixels, size_t m, const uint32_t* counts,
+                               int nsamples, const float* jitter, int table_spp, rt_ray* rays, uint32_t* seeds);
+int rt_camera_rays_pixels_device(const rt_camera* cam, const uint32_t* pixels_dev, size_t m, const uint32_t* counts_dev,
+                                 int nsamples, const float* jitter_dev, int table_spp, rt_ray* rays_dev,
+                                 uint32_t* seeds_dev, int device, void* hip_stream);
+
+typedef struct rt_afilm rt_afilm;
+typedef struct {
+    int32_t min_samples;      /* >= 2: below it a pixel is always selected */
+    int32_t max_samples;      /* no pixel goes beyond it */
+    int32_t step;             /* >= 1: the samples a selected pixel is about to get */
+    double tol;               /* >= 0: relative standard error of the mean to reach */
+    double floor;             /* > 0: the mean below which the error is absolute */
+} rt_afilm_select_opts;
+/* A width x height film on `device`, zeroed (synchronous). */
+int rt_afilm_create(int device, int width, int height, rt_afilm** out);
+void rt_afilm_destroy(rt_afilm* f);
+/* Sums, counts and moments to 0. */
+int rt_afilm_clear_device(rt_afilm* f, void* hip_stream);
+/* The device pointer to the W * H counts (NULL for a null film), valid while the film lives. */
+const uint32_t* rt_afilm_counts_device(const rt_afilm* f);
+int rt_afilm_add_device(rt_afilm* f, const uint32_t* pixels_dev, size_t m, const float* radiance_dev, int nsamples,
+                        void* hip_stream);
+int rt_afilm_resolve_device(rt_afilm* f, int row0, int rows, float* rgb_dev, uint8_t* p6_dev, uint32_t* counts_out_dev,
+                            void* hip_stream);
+size_t rt_afilm_select_scratch_bytes(const rt_afilm* f);
+int rt_afilm_select_device(rt_afilm* f, const rt_afilm_select_opts* opts, uint32_t* pixels_out_dev, uint32_t* count_dev,
+                           void* scratch_dev, void* hip_stream);
+int rt_afilm_host(int width, int height, float* sum, uint32_t* count, float* moments, const uint32_t* pixels, size_t m,
+                  const float* radiance, int nsamples, float* rgb_out, uint8_t* p6_out, const rt_afilm_select_opts* opts,
+                  uint32_t* pixels_out, uint32_t* selected_out);
 
 /* The Blinn-Phong powf of the kernels (restatement of the reference libm's powf, see
  * csrc/rt_math.hpp): rt_powf_host evaluates the host build, rt_powf_batch the device build

@@ -234,6 +234,43 @@ inline std::vector<float> film_pixels_host(const std::vector<float>& radiance, i
     return rgb;
 }
 
+// A film with a sample count and two luminance moments per pixel on a device (rt_afilm): add samples onto
+// a pixel list, resolve every pixel with its own count, select the pixels to sample next; with
+// rt_camera_rays_pixels_device (counts()) a pixel with c samples is render(spp = c)'s pixel.  Device pointers.
+class AdaptiveFilm {
+public:
+    AdaptiveFilm(int width, int height, int device = 0) : w_(width), h_(height), dev_(device) {
+        check(rt_afilm_create(device, width, height, &f_));
+    }
+    AdaptiveFilm(const AdaptiveFilm&) = delete;
+    AdaptiveFilm& operator=(const AdaptiveFilm&) = delete;
+    ~AdaptiveFilm() { if (f_) rt_afilm_destroy(f_); }
+    rt_afilm* get() const { return f_; }
+    int width() const { return w_; }
+    int height() const { return h_; }
+    int device() const { return dev_; }
+    const uint32_t* counts() const { return rt_afilm_counts_device(f_); }
+    // radiance_dev: m*nsamples*3 floats, sample s of entry k at k * nsamples + s; pixels_dev null: every pixel
+    void add(const uint32_t* pixels_dev, size_t m, const float* radiance_dev, int nsamples, void* hip_stream = nullptr) {
+        check(rt_afilm_add_device(f_, pixels_dev, m, radiance_dev, nsamples, hip_stream));
+    }
+    // rgb_dev: rows*W*3 floats, p6_dev: rows*W*3 bytes, counts_out_dev: rows*W words; two of them may be null
+    void resolve(int row0, int rows, float* rgb_dev, uint8_t* p6_dev, uint32_t* counts_out_dev, void* hip_stream = nullptr) {
+        check(rt_afilm_resolve_device(f_, row0, rows, rgb_dev, p6_dev, counts_out_dev, hip_stream));
+    }
+    size_t select_scratch_bytes() const { return rt_afilm_select_scratch_bytes(f_); }
+    // pixels_out_dev: W*H words; *count_dev: their number, written in stream order (nothing is read back)
+    void select(const rt_afilm_select_opts& opts, uint32_t* pixels_out_dev, uint32_t* count_dev, void* scratch_dev,
+                void* hip_stream = nullptr) {
+        check(rt_afilm_select_device(f_, &opts, pixels_out_dev, count_dev, scratch_dev, hip_stream));
+    }
+    void clear(void* hip_stream = nullptr) { check(rt_afilm_clear_device(f_, hip_stream)); }
+
+private:
+    rt_afilm* f_ = nullptr;
+    int w_ = 0, h_ = 0, dev_ = 0;
+};
+
 // Path stages for caller hits (rt_path_*): TraceRayIterative's loop body on caller rays and hit records,
 // with begin, compact and finish around it.  Device pointers; every call is asynchronous on hip_stream.
 inline rt_path_opts path_opts(bool diffuse_bounce = true, rt_vec3 miss_color = rt_vec3{0.f, 0.f, 0.f}, int flags = 0) {

@@ -31,6 +31,7 @@ RT_RAYS_CLOSEST, RT_RAYS_OCCLUDED = 0, 1
 RT_RAYS_VARIANT_NONE, RT_RAYS_VARIANT_WIDE, RT_RAYS_VARIANT_BINARY, RT_RAYS_VARIANT_DEEP = 0, 1, 2, 3
 RT_PATH_LAST = 16
 RT_PATH_NONE = 0xFFFFFFFF
+RT_PIXEL_NONE = 0xFFFFFFFF
 # rt_tune_id (include/rt_mi355x.h): knob name -> id
 TUNE = {"frustum_arity": 0, "half_waves": 1, "paired_only": 2, "heavy_frac": 3, "heavy_cap": 4,
         "cull_coverage": 5, "cull_boxes": 6, "big_scene_bytes": 7, "frustum_stack_cap": 8,
@@ -125,6 +126,11 @@ class PathOpts(C.Structure):
 
 class PathStateT(C.Structure):
     _fields_ = [("radiance", C.c_void_p), ("throughput", C.c_void_p), ("rng", C.c_void_p)]
+
+
+class AFilmSelectOpts(C.Structure):
+    _fields_ = [("min_samples", C.c_int32), ("max_samples", C.c_int32), ("step", C.c_int32), ("tol", C.c_double),
+                ("floor", C.c_double)]
 
 
 class Ray(C.Structure):
@@ -240,6 +246,17 @@ SIGNATURES = {
     "rt_path_compact_scratch_bytes": (SZ, [SZ]),
     "rt_path_compact_device": (I, [I, SZ, P, P, P, P, P, P, P, P]),
     "rt_path_finish_device": (I, [I, SZ, P, P]),
+    "rt_camera_rays_pixels_host": (I, [P, P, SZ, P, I, P, I, P, P]),
+    "rt_camera_rays_pixels_device": (I, [P, P, SZ, P, I, P, I, P, P, I, P]),
+    "rt_afilm_create": (I, [I, I, I, P]),
+    "rt_afilm_destroy": (None, [P]),
+    "rt_afilm_clear_device": (I, [P, P]),
+    "rt_afilm_counts_device": (P, [P]),
+    "rt_afilm_add_device": (I, [P, P, SZ, P, I, P]),
+    "rt_afilm_resolve_device": (I, [P, I, I, P, P, P, P]),
+    "rt_afilm_select_scratch_bytes": (SZ, [P]),
+    "rt_afilm_select_device": (I, [P, P, P, P, P, P]),
+    "rt_afilm_host": (I, [I, I, P, P, P, P, SZ, P, I, P, P, P, P, P]),
     "rt_powf_host": (C.c_float, [C.c_float, C.c_float]),
     "rt_debug_frustum_records": (C.c_int, [C.c_size_t, P, P, C.c_int, C.c_int, P, P, C.c_size_t]),
     "rt_debug_scene_pack": (I, [SZ, P, P, P, P, P]),

@@ -528,6 +528,69 @@ class DeviceScene:
             if own:
                 film.close()
 
+    def render_adaptive(self, camera: Camera, min_spp: int, max_spp: int, step_spp: int, tol: float, max_depth: int = 1,
+                        diffuse_bounce: bool = True, miss_color=(0, 0, 0), jitter=None, ray_fn=None, material_fn=None,
+                        p6: bool = False, film: Optional["AdaptiveFilm"] = None):
+        """A frame with per-pixel sample counts, on the device: one dense pass of ``min_spp``
+        samples, then ``AdaptiveFilm.select -> camera_rays_pixels -> ray_fn -> shade_rays |
+        trace_paths -> AdaptiveFilm.add`` with ``step_spp`` samples for the selected pixels until
+        none is selected, then one resolve.  A pixel goes on while its count + step_spp <= max_spp
+        and the standard error of its mean luminance exceeds ``tol`` times the mean (see
+        AdaptiveFilm.select).  Every pixel gets its samples 0, 1, ... in order from the frame's
+        jitter table, so a pixel that ends with c samples is render(spp=c)'s pixel bit for bit;
+        ``tol=0`` with max_spp - min_spp a multiple of step_spp is render(spp=max_spp).
+
+        ``jitter``: (max_spp, 2) float32, None for jittered_samples(max_spp).
+        ``ray_fn(rays, seeds, pixels, counts, n) -> rays`` as in render_rays: the pass's pinhole rays
+        ((m*n, 6), entry k's n samples together), their seeds, the pixel indices y*W+x ((m,) int32)
+        and the film's count map ((W*H,) int32, the samples each pixel had before this pass).
+        ``material_fn``: radiance from trace_paths with that hook instead of shade_rays.
+        ``film``: an AdaptiveFilm of the camera's size to go on from (not cleared before, not
+        closed after); default a new one, closed on return.
+        One 4-byte read of the selected count per pass is the only host synchronisation.
+        Returns ``(rgb, counts)`` [``, bytes`` with ``p6=True``]: (H, W, 3) float32, (H, W) int32
+        samples per pixel, (H, W, 3) uint8 P6 samples."""
+        import torch
+
+        W, H = camera.pixel_width, camera.pixel_height
+        min_spp, max_spp, step_spp = int(min_spp), int(max_spp), int(step_spp)
+        if min_spp < 2 or max_spp < min_spp or step_spp < 1:
+            raise ValueError("render_adaptive: needs 2 <= min_spp <= max_spp and step_spp >= 1")
+        jit = (jittered_samples(max_spp) if jitter is None else _c(jitter, np.float32)).reshape(-1, 2)
+        if jit.shape[0] < max_spp:
+            raise ValueError("render_adaptive: jitter must hold (max_spp, 2) floats")
+        dev = self._torch_dev()
+        own = film is None
+        if own:
+            film = AdaptiveFilm(W, H, self.device)
+        elif (film.width, film.height, film.device) != (W, H, self.device):
+            raise ValueError("render_adaptive: the film is not of the camera's size on the scene's device")
+
+        def shade(pixels, n):
+            rays, seeds = camera_rays_pixels(camera, pixels, film, n, jd, device=self.device)
+            if ray_fn is not None:
+                shown = pixels if pixels is not None else torch.arange(W * H, dtype=torch.int32, device=dev)
+                rays = ray_fn(rays, seeds, shown, film.counts, n)
+            if material_fn is None:
+                rad = self.shade_rays(rays, seeds, max_depth, diffuse_bounce, miss_color)
+            else:
+                rad = self.trace_paths(rays, seeds, max_depth, diffuse_bounce, miss_color, material_fn=material_fn)
+            film.add(rad, pixels, n)
+
+        try:
+            jd = torch.from_numpy(np.ascontiguousarray(jit)).to(dev)
+            shade(None, min_spp)
+            while True:
+                pixels, m = film.select(min_spp, max_spp, step_spp, tol)
+                if m == 0:
+                    break
+                shade(pixels, step_spp)
+            out = film.resolve(p6=p6, counts=True)
+            return (out[0], out[1].view(H, W), out[2]) if p6 else (out[0], out[1].view(H, W))
+        finally:
+            if own:
+                film.close()
+
     def trace_hits(self, rays, flags: int = 0, stream: Optional[int] = None, timing: bool = False):
         """Hit records of caller rays (rt_trace_hits / rt_trace_hits_device): per ray the HitRecord
         SearchBVH returns (G/include/query.h:224-311, intersectTriangle's tail :110-130) with the ids
@@ -1168,6 +1231,295 @@ class Film:
             self.close()
         except Exception:
             pass
+
+
+def camera_rays_pixels(camera: Camera, pixels, counts, nsamples: int, jitter, device: Optional[int] = None,
+                       stream: Optional[int] = None):
+    """Camera rays for a list of pixels (rt_camera_rays_pixels_host / _device): ``pixels`` holds m
+    indices y * W + x in any order (None: every pixel in order), ``counts`` the W * H samples each
+    pixel already has (None: 0), and ray k * nsamples + s is sample ``counts[pixels[k]] + s`` of
+    that pixel, Camera::get_ray with that row of ``jitter`` and the seed make_rng_seed(x, y,
+    counts + s).  ``jitter``: the whole frame's table, (table_spp, 2) float32, or an int table_spp
+    for jittered_samples(table_spp).  An index >= W * H (RT_PIXEL_NONE) gives origin = center,
+    direction 0, seed 0; a sample past the table reads its last row.
+
+    ``device=None``: the host build over numpy arrays (uint32 ``pixels`` and ``counts``), numpy
+    ``(rays (m*nsamples, 6) float32, seeds (m*nsamples,) uint32)``.  An int device: one launch on
+    ``stream`` of that device (default torch's current stream); ``pixels`` and ``counts`` are int32
+    tensors there (the words' 32 bits; ``counts`` may be an AdaptiveFilm, for its count map),
+    ``jitter`` may be a float32 tensor there as well, and torch tensors ``(rays, seeds (int32))``
+    are returned with no host synchronisation."""
+    nsamples = int(nsamples)
+    W, H = camera.pixel_width, camera.pixel_height
+    if device is None:
+        px = None if pixels is None else _c(pixels, np.uint32).reshape(-1)
+        ct = None if counts is None else _c(counts, np.uint32).reshape(-1)
+        if ct is not None and ct.size != W * H:
+            raise ValueError("camera_rays_pixels: counts must hold W * H words")
+        m = W * H if px is None else px.size
+        if isinstance(jitter, (int, np.integer)):
+            jit, table = None, int(jitter)
+        else:
+            jit = _c(jitter, np.float32).reshape(-1)
+            if jit.size % 2 != 0:
+                raise ValueError("camera_rays_pixels: jitter must hold (table_spp, 2) floats")
+            table = jit.size // 2
+        n = m * max(nsamples, 0)
+        rays = np.zeros((max(n, 1), 6), np.float32)[:n]
+        seeds = np.zeros(max(n, 1), np.uint32)[:n]
+        check(lib().rt_camera_rays_pixels_host(C.byref(camera.c), ptr(px), m, ptr(ct), nsamples, ptr(jit), table, ptr(rays),
+                                               ptr(seeds)))
+        return rays, seeds
+    import torch
+
+    dev = torch.device("cuda", int(device))
+
+    def words(a, who):
+        if a is None:
+            return None
+        if type(a).__module__.split(".")[0] != "torch":
+            a = torch.from_numpy(_c(a, np.uint32).view(np.int32)).to(dev)
+        if a.device != dev or a.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+            raise ValueError(f"camera_rays_pixels: {who} must be an int32 or uint32 tensor on {dev}")
+        return a.contiguous().view(-1)
+
+    cur = torch.cuda.current_stream(dev)
+    foreign = stream is not None and stream != cur.cuda_stream
+    px = words(pixels, "pixels")
+    m = W * H if px is None else px.numel()
+    if isinstance(counts, AdaptiveFilm):
+        if (counts.width, counts.height, counts.device) != (W, H, int(device)):
+            raise ValueError("camera_rays_pixels: the film is not of the camera's size on that device")
+        ct, cp = None, counts._counts_ptr()
+    else:
+        ct = words(counts, "counts")
+        if ct is not None and ct.numel() != W * H:
+            raise ValueError("camera_rays_pixels: counts must hold W * H words")
+        cp = None if ct is None else ct.data_ptr()
+    if isinstance(jitter, (int, np.integer)):
+        jitter = jittered_samples(int(jitter))
+    if type(jitter).__module__.split(".")[0] == "torch":
+        if jitter.device != dev or jitter.dtype != torch.float32 or jitter.numel() % 2 != 0:
+            raise ValueError(f"camera_rays_pixels: jitter must be a (table_spp, 2) float32 tensor on {dev}")
+        jd = jitter.contiguous()
+    else:
+        jit = _c(jitter, np.float32).reshape(-1)
+        if jit.size % 2 != 0:
+            raise ValueError("camera_rays_pixels: jitter must hold (table_spp, 2) floats")
+        jd = torch.from_numpy(jit).to(dev)  # on torch's current stream
+    table = jd.numel() // 2
+    n = m * max(nsamples, 0)
+    # (an empty tensor has no address: one spare element keeps the C checks' answers the same)
+    rays = torch.empty((max(n, 1), 6), dtype=torch.float32, device=dev)[:n]
+    seeds = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    spare = torch.empty(2, dtype=torch.float32, device=dev) if table == 0 else None
+    if foreign:  # what was made on torch's stream must be there before the caller's stream reads it
+        cur.synchronize()
+    st = stream if foreign else cur.cuda_stream
+    check(lib().rt_camera_rays_pixels_device(C.byref(camera.c), None if px is None or m == 0 else px.data_ptr(), m, cp,
+                                             nsamples, jd.data_ptr() if spare is None else spare.data_ptr(), table,
+                                             rays.data_ptr(), seeds.data_ptr(), int(device), st))
+    if foreign:  # ... and stay until that launch has read it
+        ext = torch.cuda.ExternalStream(stream, device=dev)
+        for t in (jd, px, ct):
+            if t is not None:
+                t.record_stream(ext)
+    return rays, seeds
+
+
+class _DeviceWords:
+    """W * H 32-bit words of device memory owned by a native object, for torch.as_tensor."""
+
+    def __init__(self, address: int, n: int, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i4", "data": (address, False), "version": 2,
+                                         "strides": None}
+
+
+class AdaptiveFilm:
+    """A film with a sample count per pixel (rt_afilm): per pixel render()'s three float sums, a
+    count, and two float moments of the sample luminance, 24 bytes, all on the device.  ``add``
+    puts samples onto listed pixels in order, ``resolve`` divides every pixel by its own count,
+    ``select`` names the pixels whose mean is still uncertain.  Fed each pixel's samples 0, 1, ...
+    in order (camera_rays_pixels with this film's counts), a pixel with c samples is render(spp=c)'s
+    pixel bit for bit.  Calls are launches on ``stream`` (a HIP stream handle; default torch's
+    current stream) with no host synchronisation, select's returned count excepted."""
+
+    def __init__(self, width: int, height: int, device: int = 0):
+        h = C.c_void_p()
+        check(lib().rt_afilm_create(int(device), int(width), int(height), C.byref(h)))
+        self._h = h
+        self.width, self.height, self.device = int(width), int(height), int(device)
+        self._scratch = None
+        self._count = None
+
+    def _handle(self) -> C.c_void_p:
+        if not self._h:
+            raise L.RTError(-1, "film is closed")
+        return self._h
+
+    def _dev(self):
+        import torch
+
+        return torch.device("cuda", self.device)
+
+    def _counts_ptr(self) -> int:
+        return int(lib().rt_afilm_counts_device(self._handle()))
+
+    @property
+    def counts(self):
+        """The (W*H,) int32 tensor view of the film's per-pixel sample counts: the device memory
+        itself, valid until close() and changed by add and clear in stream order."""
+        import torch
+
+        return torch.as_tensor(_DeviceWords(self._counts_ptr(), self.width * self.height, self), device=self._dev())
+
+    def add(self, radiance, pixels=None, nsamples: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """Add ``nsamples`` samples to each listed pixel: ``pixels`` an (m,) int32 tensor of indices
+        y * W + x, unique within the call (None: every pixel in order; an index outside the image
+        is skipped), ``radiance`` a float32 tensor of m*nsamples*3 elements, sample s of entry k at
+        k * nsamples + s, the order of camera_rays_pixels and of shade_rays' output.  ``nsamples``
+        None: what the tensor's size gives."""
+        import torch
+
+        dev = self._dev()
+        if radiance.device != dev or radiance.dtype != torch.float32:
+            raise ValueError(f"AdaptiveFilm.add: expects a float32 tensor on {dev}")
+        if pixels is not None and (pixels.device != dev or pixels.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                   or pixels.dim() != 1 or not pixels.is_contiguous()):
+            raise ValueError(f"AdaptiveFilm.add: pixels must be a contiguous (m,) int32 tensor on {dev}")
+        radiance = radiance.contiguous()
+        m = self.width * self.height if pixels is None else pixels.numel()
+        if nsamples is None:
+            nsamples = radiance.numel() // (3 * m) if m > 0 else 1
+        if radiance.numel() != 3 * m * int(nsamples):
+            raise ValueError("AdaptiveFilm.add: radiance must hold m * nsamples * 3 floats")
+        if m == 0:
+            return
+        check(lib().rt_afilm_add_device(self._handle(), None if pixels is None else pixels.data_ptr(), m, radiance.data_ptr(),
+                                        int(nsamples), _stream_of(stream, dev)))
+
+    def resolve(self, p6: bool = False, counts: bool = False, row0: int = 0, rows: Optional[int] = None,
+                stream: Optional[int] = None):
+        """The pixels of rows [row0, row0 + rows) (default: to the last row), each from its own
+        count (no samples: 0): a (rows, W, 3) float32 tensor ``rgb``, or ``(rgb[, counts][, bytes])``:
+        with ``counts=True`` the rows' (rows, W) int32 sample-count map, with ``p6=True`` the
+        (rows, W, 3) uint8 P6 samples (write_p6 defaults).  Does not clear."""
+        import torch
+
+        if rows is None:
+            rows = self.height - int(row0)
+        dev = self._dev()
+        r = max(int(rows), 0)
+        rgb = torch.empty((r, self.width, 3), dtype=torch.float32, device=dev)
+        b = torch.empty((r, self.width, 3), dtype=torch.uint8, device=dev) if p6 else None
+        c = torch.empty((r, self.width), dtype=torch.int32, device=dev) if counts else None
+        spare = torch.empty(1, dtype=torch.float32, device=dev) if rgb.numel() == 0 else None
+        check(lib().rt_afilm_resolve_device(self._handle(), int(row0), int(rows),
+                                            rgb.data_ptr() if spare is None else spare.data_ptr(),
+                                            None if b is None or spare is not None else b.data_ptr(),
+                                            None if c is None or spare is not None else c.data_ptr(), _stream_of(stream, dev)))
+        out = (rgb,) + ((c,) if counts else ()) + ((b,) if p6 else ())
+        return out if len(out) > 1 else rgb
+
+    def select(self, min_spp: int, max_spp: int, step: int, tol: float, floor: float = 1e-3, stream: Optional[int] = None):
+        """The pixels to sample next (rt_afilm_select_device): a pixel with n samples is selected
+        iff n + step <= max_spp and (n < min_spp or its mean is noisy): in double from the float
+        moments, mean = m1 / n, var = (max(0, m2 / n - mean^2) * n) / (n - 1), noisy iff
+        var / n > (tol * max(mean, floor))^2, the squared standard error of the mean luminance
+        against the squared tolerance.  ``min_spp`` >= 2, ``step`` >= 1, ``tol`` >= 0, ``floor`` > 0.
+
+        Returns ``(pixels, n)``: ``pixels`` an (n,) int32 device tensor of indices y * W + x in
+        increasing order, ``n`` a Python int.  Reading ``n`` is one 4-byte host read per pass, which
+        waits for the stream: the only synchronisation of an adaptive pass."""
+        import torch
+
+        dev = self._dev()
+        o = L.AFilmSelectOpts(int(min_spp), int(max_spp), int(step), float(tol), float(floor))
+        if self._scratch is None:
+            nb = int(lib().rt_afilm_select_scratch_bytes(self._handle()))
+            self._scratch = torch.empty((nb + 3) // 4, dtype=torch.int32, device=dev)
+            self._count = torch.empty(1, dtype=torch.int32, device=dev)
+        out = torch.empty(self.width * self.height, dtype=torch.int32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        st = _stream_of(stream, dev)
+        check(lib().rt_afilm_select_device(self._handle(), C.byref(o), out.data_ptr(), self._count.data_ptr(),
+                                           self._scratch.data_ptr(), st))
+        if st != cur.cuda_stream:
+            torch.cuda.ExternalStream(st, device=dev).synchronize()
+        n = int(self._count.item())
+        return out[:n], n
+
+    def clear(self, stream: Optional[int] = None) -> None:
+        """Sums, counts and moments to 0."""
+        check(lib().rt_afilm_clear_device(self._handle(), _stream_of(stream, self._dev())))
+
+    def close(self) -> None:
+        if self._h:
+            lib().rt_afilm_destroy(self._h)
+            self._h = C.c_void_p()
+            self._scratch = self._count = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def afilm_host(width: int, height: int, state=None, radiance=None, pixels=None, nsamples: Optional[int] = None,
+               resolve: bool = False, select=None):
+    """Host build of the adaptive film (rt_afilm_host, no device).  ``state``: ``(sums (H*W*3,)
+    float32, counts (H*W,) uint32, moments (H*W*2,) float32)``, updated in place (None: zeros).
+    In this order: ``radiance`` (m*nsamples*3 float32; None: no add) is added onto ``pixels`` ((m,)
+    uint32; None: every pixel in order); with ``resolve`` the whole image's ``rgb`` (H, W, 3)
+    float32 and P6 ``bytes`` (H, W, 3) uint8; with ``select = (min_spp, max_spp, step, tol[, floor])``
+    the selected pixel indices.  Returns a dict: ``state``, and ``rgb``, ``bytes``, ``selected``
+    where asked for."""
+    width, height = int(width), int(height)
+    np_ = max(width * height, 0)
+    if state is None:
+        state = (np.zeros(np_ * 3, np.float32), np.zeros(np_, np.uint32), np.zeros(np_ * 2, np.float32))
+    sums, counts, mom = state
+    for a, dt, k in ((sums, np.float32, 3), (counts, np.uint32, 1), (mom, np.float32, 2)):
+        if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.flags.writeable and a.size == np_ * k):
+            raise ValueError("afilm_host: the state must be writeable contiguous arrays of W*H*3, W*H and W*H*2 elements")
+    rad = px = None
+    m = 0
+    if radiance is not None:
+        rad = _c(radiance, np.float32).reshape(-1)
+        px = None if pixels is None else _c(pixels, np.uint32).reshape(-1)
+        m = np_ if px is None else px.size
+        if nsamples is None:
+            nsamples = rad.size // (3 * m) if m > 0 else 1
+        if rad.size != 3 * m * max(int(nsamples), 0):
+            raise ValueError("afilm_host: radiance must hold m * nsamples * 3 floats")
+        if rad.size == 0:
+            rad = np.zeros(1, np.float32)  # (an empty array still has an address for the C checks)
+    rgb = np.zeros((height, width, 3), np.float32) if resolve else None
+    b = np.zeros((height, width, 3), np.uint8) if resolve else None
+    o = None
+    sel = n_sel = None
+    if select is not None:
+        mn, mx, stp, tol = select[:4]
+        o = L.AFilmSelectOpts(int(mn), int(mx), int(stp), float(tol), float(select[4]) if len(select) > 4 else 1e-3)
+        sel = np.zeros(max(np_, 1), np.uint32)
+        n_sel = C.c_uint32(0)
+    check(lib().rt_afilm_host(width, height, ptr(sums), ptr(counts), ptr(mom), ptr(px) if px is not None and px.size else None,
+                              m, ptr(rad), int(nsamples) if nsamples is not None else 1, ptr(rgb), ptr(b),
+                              C.byref(o) if o is not None else None, ptr(sel), C.byref(n_sel) if n_sel is not None else None))
+    out = {"state": state}
+    if resolve:
+        out["rgb"], out["bytes"] = rgb, b
+    if select is not None:
+        out["selected"] = sel[:n_sel.value].copy()
+    return out
 
 
 def _stream_of(stream, dev):

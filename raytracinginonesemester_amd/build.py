@@ -7,7 +7,7 @@
   device translation units (hipcc --offload-arch=gfx950): rt_device.hip (scene upload + render;
   its device code in the rt_wave/instrument/traverse/shade/prepass/query/path.hpp sections),
   rt_hw1.hip (the HW1 path),
-  rt_frame.hip (P6 quantisation and strip un-permute on the device), rt_lbvh.hip (LBVH build on
+  rt_frame.hip (P6 quantisation, strip un-permute, the film and the adaptive film on the device), rt_lbvh.hip (LBVH build on
   the device), rt_renderer.hip (the multi-GPU frame renderer).  Units compile in parallel.
   Every float path is compiled with -ffp-contract=off and without fast-math; HIP's default
   correctly rounded f32 division / sqrt stay on (parity with the reference CPU build).

@@ -36,6 +36,7 @@
 //   rt_prepass.hpp     tile bounds, root and tree-cut culling passes, work lists
 //   rt_query.hpp       batched ray queries on a resident scene (rt_trace_rays*, rt_shade_rays*)
 //   rt_path.hpp        path stages for caller hits (rt_path_*): step, begin, compaction, finish
+//   rt_scan.hpp        the compaction's scan of tile counts (through rt_path.hpp; also used by rt_frame.hip)
 // Separate translation units: rt_scene_pack.cpp (the host half of rt_scene_create: checks, ids,
 // stack bounds, every packed array), rt_records.cpp (host record builders), rt_hw1.hip (the HW1
 // path), rt_frame.hip, rt_lbvh.hip, rt_renderer.hip.
@@ -2008,29 +2009,6 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     return a && b && na && nb && x < y + nb && y < x + na;
 }
 
-// Tiles of n entries, and the scratch words of a scan over n entries that recurses through them.
-size_t path_tiles(size_t n) { return (n + PATH_TILE - 1) / PATH_TILE; }
-size_t path_scan_words(size_t n) {
-    size_t words = 0;
-    while (n > PATH_TILE) {
-        n = path_tiles(n);
-        words += n;
-    }
-    return words;
-}
-
-// a[0..n) to exclusive prefix sums in place, the sum to *total: one launch for one tile, else the
-// tiles' sums (the next words of scratch), their scan, and the tiles' scans from those offsets.
-void path_scan(uint32_t* a, size_t n, uint32_t* scratch, uint32_t* total, hipStream_t st) {
-    if (n <= PATH_TILE) {
-        hipLaunchKernelGGL(path_scan_kernel, dim3(1), dim3(BLOCK), 0, st, a, uint32_t(n), nullptr, total);
-        return;
-    }
-    const size_t nt = path_tiles(n);
-    hipLaunchKernelGGL(path_tile_sums_kernel, dim3(unsigned(nt)), dim3(BLOCK), 0, st, a, uint32_t(n), scratch);
-    path_scan(scratch, nt, scratch + nt, total, st);
-    hipLaunchKernelGGL(path_scan_kernel, dim3(unsigned(nt)), dim3(BLOCK), 0, st, a, uint32_t(n), scratch, nullptr);
-}
 }  // namespace
 
 extern "C" int rt_path_begin_device(int device, size_t n, const uint32_t* seeds, const rt_path_state* state, void* stream) {

@@ -231,9 +231,8 @@ __global__ __launch_bounds__(BLOCK) void path_finish_kernel(float* __restrict__ 
 // base + j * BLOCK + t belongs to thread t in round j (coalesced), and its rank is the live
 // entries of the rounds and waves before it plus the live lanes below it in its wave's ballot:
 // increasing k, so the order is stable.
-constexpr int PATH_ROUNDS = 8;
-constexpr uint32_t PATH_TILE = BLOCK * PATH_ROUNDS;  // 2048
-constexpr int PATH_WAVES = BLOCK / 64;
+// (the tile constants and the scan of the counts: rt_scan.hpp, shared with the adaptive film)
+#include "rt_scan.hpp"
 
 __global__ __launch_bounds__(BLOCK) void path_count_kernel(const uint8_t* __restrict__ alive, uint32_t m,
                                                            uint32_t* __restrict__ counts) {
@@ -253,59 +252,6 @@ __global__ __launch_bounds__(BLOCK) void path_count_kernel(const uint8_t* __rest
         for (int w = 0; w < PATH_WAVES; ++w) s += part[w];
         counts[blockIdx.x] = s;
     }
-}
-
-// The sum of each tile of a[0..n) (the scan's way up).
-__global__ __launch_bounds__(BLOCK) void path_tile_sums_kernel(const uint32_t* __restrict__ a, uint32_t n,
-                                                               uint32_t* __restrict__ sums) {
-    __shared__ uint32_t part[BLOCK];
-    const uint64_t base = (uint64_t)blockIdx.x * PATH_TILE;
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j < PATH_ROUNDS; ++j) {
-        const uint64_t i = base + (uint32_t)j * BLOCK + threadIdx.x;
-        if (i < n) s += a[i];
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = BLOCK / 2; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) part[threadIdx.x] += part[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = part[0];
-}
-
-// a[0..n) to its exclusive prefix sums in place, tile by tile: tile b starts at tile_off[b] (null:
-// one tile, from 0); total (with one tile; may be null) receives the sum of all.  A thread scans
-// PATH_ROUNDS consecutive entries, the block the threads' sums (Hillis-Steele in LDS).
-__global__ __launch_bounds__(BLOCK) void path_scan_kernel(uint32_t* __restrict__ a, uint32_t n,
-                                                          const uint32_t* __restrict__ tile_off,
-                                                          uint32_t* __restrict__ total) {
-    __shared__ uint32_t part[2][BLOCK];
-    const uint64_t first = (uint64_t)blockIdx.x * PATH_TILE + (uint64_t)threadIdx.x * PATH_ROUNDS;
-    uint32_t v[PATH_ROUNDS];
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j < PATH_ROUNDS; ++j) {
-        v[j] = first + (uint32_t)j < n ? a[first + (uint32_t)j] : 0u;
-        s += v[j];
-    }
-    int cur = 0;
-    part[0][threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < BLOCK; d <<= 1) {
-        const uint32_t x = part[cur][threadIdx.x] + ((int)threadIdx.x >= d ? part[cur][threadIdx.x - d] : 0u);
-        part[cur ^ 1][threadIdx.x] = x;
-        cur ^= 1;
-        __syncthreads();
-    }
-    uint32_t run = (tile_off != nullptr ? tile_off[blockIdx.x] : 0u) + part[cur][threadIdx.x] - s;
-#pragma unroll
-    for (int j = 0; j < PATH_ROUNDS; ++j) {
-        if (first + (uint32_t)j < n) a[first + (uint32_t)j] = run;
-        run += v[j];
-    }
-    if (total != nullptr && threadIdx.x == BLOCK - 1) *total = part[cur][BLOCK - 1];
 }
 
 struct PathScatterParams {
