@@ -44,7 +44,11 @@ extern "C" {
                                  rt_camera_rays_pixels_device, rt_afilm, rt_afilm_select_opts,
                                  rt_afilm_create, rt_afilm_destroy, rt_afilm_clear_device,
                                  rt_afilm_counts_device, rt_afilm_add_device, rt_afilm_resolve_device,
-                                 rt_afilm_select_scratch_bytes, rt_afilm_select_device, rt_afilm_host */
+                                 rt_afilm_select_scratch_bytes, rt_afilm_select_device, rt_afilm_host;
+                                 rt_scene_create_refittable, rt_scene_refit_device, rt_scene_refit,
+                                 rt_refit_aabbs_host, rt_triangles_from_mesh_device,
+                                 rt_debug_scene_digest, rt_debug_scene_refit_pack,
+                                 rt_debug_scene_refit_chain */
 
 enum {
     RT_OK = 0,
@@ -202,6 +206,42 @@ void rt_scene_destroy(rt_scene* s);
 int rt_scene_clone(const rt_scene* src, int device, rt_scene** out);
 int rt_scene_device(const rt_scene* s);
 size_t rt_scene_device_bytes(const rt_scene* s);
+
+/* ---- refit: new vertex positions under a resident scene ---------------------- */
+/* rt_scene_create's scene, its packed arrays byte for byte, plus what a refit needs on the device
+ * (counted in rt_scene_device_bytes).  RT_ERR_UNSUPPORTED, creating nothing, unless the tree is
+ * proper (every one of the 2P-1 nodes reached from node 0, once; two children per internal node;
+ * every leaf naming a triangle), and when quantised records are in force (RT_TUNE_QUANT_RECORDS).
+ * Trees that take the binary records and deep trees are supported.  rt_scene_clone of such a scene
+ * is refittable too. */
+int rt_scene_create_refittable(int device, size_t num_triangles, const rt_bvh_node* nodes, const rt_aabb* aabbs,
+                               const rt_triangle* triangles, const int32_t* tri_object_ids,
+                               const rt_material* materials, int num_materials, const rt_light* lights,
+                               int num_lights, rt_scene** out);
+/* Move the scene's triangles: tris_dev holds the P triangles on the scene's device, in the order
+ * given at creation (normals included).  The tree and the record topology chosen at creation
+ * stay; the leaf boxes are aabb_of_triangle's, the internal boxes merge(left, right) bottom-up
+ * (rt_refit_aabbs_host), and every stored box, v0 | e1 | e2 and normal is rewritten from them, so
+ * every query answers as the reference does on (nodes, those boxes, the new triangles).  A first
+ * pass checks every vertex coordinate: RT_ERR_ARG, the scene untouched, if one is not finite.
+ * The call waits for the scene's own streams and for hip_stream before it writes, runs on
+ * hip_stream and synchronises it before returning; *ms (optional) is the HIP-event time of its
+ * launches.  Frames and queries the caller has queued on OTHER streams are the caller's to order
+ * against it.  The per-tile cost history is forgotten.  A long animation degrades the tree: the
+ * topology is not rebuilt (rt_build_bvh_device and a new scene do that).  RT_ERR_UNSUPPORTED for
+ * a scene not created refittable. */
+int rt_scene_refit_device(rt_scene* s, const rt_triangle* tris_dev, void* hip_stream, float* ms);
+/* The same from host memory. */
+int rt_scene_refit(rt_scene* s, const rt_triangle* tris_host, float* ms);
+/* The boxes a refit gives the tree (2P-1, by node), on the host.  RT_ERR_UNSUPPORTED unless the
+ * tree is proper. */
+int rt_refit_aabbs_host(size_t num_triangles, const rt_bvh_node* nodes, const rt_triangle* tris, rt_aabb* aabbs_out);
+/* The triangle array of an indexed mesh on the device (G/src/main.cu:388-404; zero normals when
+ * normals_dev is NULL), so deformed vertex buffers reach a refit without leaving the GPU.  Runs on
+ * hip_stream and synchronises it; out-of-range indices are reported as RT_ERR_ARG. */
+int rt_triangles_from_mesh_device(int device, const rt_vec3* positions_dev, size_t num_vertices,
+                                  const rt_vec3* normals_dev, const uint32_t* indices_dev, size_t num_triangles,
+                                  rt_triangle* tris_dev, void* hip_stream);
 
 enum {
     RT_KERNEL_AUTO = 0,      /* the fastest parity-equivalent kernel */
@@ -915,6 +955,17 @@ int rt_debug_frustum_records(size_t P, const rt_bvh_node* nodes, const rt_aabb* 
  * 64-bit FNV-1a hash of its bytes.  Errors as rt_scene_create reports them for these arrays. */
 int rt_debug_scene_pack(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
                         int64_t info[21], uint64_t digests[22]);
+/* The same words for a resident scene: its arrays read back from the device and hashed (waits for
+ * the device). */
+int rt_debug_scene_digest(rt_scene* s, int64_t info[21], uint64_t digests[22]);
+/* rt_debug_scene_pack of (nodes, aabbs, tris), then the host restatement of rt_scene_refit with
+ * new_tris (no device): what rt_debug_scene_digest answers after rt_scene_create_refittable and
+ * that refit.  Errors as those two calls report them. */
+int rt_debug_scene_refit_pack(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                              const rt_triangle* new_tris, int64_t info[21], uint64_t digests[22]);
+/* ... with n refits in turn: poses[0], then poses[1], ... (P triangles each). */
+int rt_debug_scene_refit_chain(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                               int n, const rt_triangle* const* poses, int64_t info[21], uint64_t digests[22]);
 
 /* Durations (ms) of the render kernel of the most recent min(max, launches, 256) timed
  * rt_render_device calls on this scene, oldest first, measured with HIP events recorded

@@ -11,6 +11,6 @@ from ._lib import (RTError, RT_DELIVER_DEVICE, RT_DELIVER_F32, RT_DELIVER_NONE, 
 from .api import (  # noqa: F401
     HIT_DTYPE, LIGHT_DTYPE, AdaptiveFilm, Camera, DeviceScene, Film, HostScene, HW1Scene, MeshHW1, Renderer, build_bvh, comm_unique_id, build_bvh_device, default_material, device_count,
     afilm_host, camera_rays, camera_rays_pixels, film_pixels_host, encode_p6, encode_p6_device, hit_fields, hit_record_host, intersect_rays, jittered_samples, p6_header, quantize_p6_device, read_p6,
-    PathState, compact_paths, path_finish, path_step_host,
+    PathState, compact_paths, path_finish, path_step_host, refit_aabbs, triangles_from_mesh,
     render, render_hw1, hw1_rects_host, unpermute_strips_device, write_p6, set_tuning, get_tuning, reset_tuning, tuning,
 )

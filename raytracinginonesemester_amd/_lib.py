@@ -181,6 +181,11 @@ SIGNATURES = {
     "rt_scene_clone": (I, [P, I, P]),
     "rt_scene_device": (I, [P]),
     "rt_scene_device_bytes": (SZ, [P]),
+    "rt_scene_create_refittable": (I, [I, SZ, P, P, P, P, P, I, P, I, P]),
+    "rt_scene_refit_device": (I, [P, P, P, P]),
+    "rt_scene_refit": (I, [P, P, P]),
+    "rt_refit_aabbs_host": (I, [SZ, P, P, P]),
+    "rt_triangles_from_mesh_device": (I, [I, P, SZ, P, P, SZ, P, P]),
     "rt_render_opts_default": (None, [P]),
     "rt_shard_rows": (I, [I, I, I, I]),
     "rt_render_device": (I, [P, P, P, P, P, P, P]),
@@ -260,6 +265,9 @@ SIGNATURES = {
     "rt_powf_host": (C.c_float, [C.c_float, C.c_float]),
     "rt_debug_frustum_records": (C.c_int, [C.c_size_t, P, P, C.c_int, C.c_int, P, P, C.c_size_t]),
     "rt_debug_scene_pack": (I, [SZ, P, P, P, P, P]),
+    "rt_debug_scene_digest": (I, [P, P, P]),
+    "rt_debug_scene_refit_pack": (I, [SZ, P, P, P, P, P, P]),
+    "rt_debug_scene_refit_chain": (I, [SZ, P, P, P, I, P, P, P]),
     "rt_powf_batch": (I, [I, P, P, I, P]),
     "rt_box_test_host": (I, [P, P, P, I, P, P, P]),
     "rt_box_test_batch": (I, [I, P, P, P, P, P, I, P]),

@@ -189,10 +189,11 @@ def _c(a, dtype):
 
 
 class DeviceScene:
-    """Reference arrays uploaded to one device (rt_scene_create)."""
+    """Reference arrays uploaded to one device (rt_scene_create; ``refittable=True``:
+    rt_scene_create_refittable, the same scene plus what ``refit`` needs on the device)."""
 
     def __init__(self, num_triangles: int, nodes, aabbs, triangles, tri_object_ids=None,
-                 materials=None, lights=None, device: int = 0):
+                 materials=None, lights=None, device: int = 0, refittable: bool = False):
         P = int(num_triangles)
         self._keep = [_c(nodes, np.uint32), _c(aabbs, np.float32), _c(triangles, np.float32)]
         objs = None if tri_object_ids is None else _c(tri_object_ids, np.int32)
@@ -201,8 +202,9 @@ class DeviceScene:
         nmat = 0 if mats is None else mats.shape[0]
         nl = 0 if lts is None else lts.shape[0]
         h = C.c_void_p()
-        check(lib().rt_scene_create(int(device), P, ptr(self._keep[0]), ptr(self._keep[1]), ptr(self._keep[2]),
-                                    ptr(objs), ptr(mats), nmat, ptr(lts), nl, C.byref(h)))
+        create = lib().rt_scene_create_refittable if refittable else lib().rt_scene_create
+        check(create(int(device), P, ptr(self._keep[0]), ptr(self._keep[1]), ptr(self._keep[2]),
+                     ptr(objs), ptr(mats), nmat, ptr(lts), nl, C.byref(h)))
         self._h = h
         self._owned = True
         self.num_triangles = P
@@ -227,9 +229,43 @@ class DeviceScene:
         return self._h
 
     @classmethod
-    def from_host(cls, hs: HostScene, device: int = 0) -> "DeviceScene":
+    def from_host(cls, hs: HostScene, device: int = 0, refittable: bool = False) -> "DeviceScene":
         return cls(hs.num_triangles, hs.nodes, hs.aabbs, hs.triangles, hs.tri_object_ids, hs.materials,
-                   hs.lights, device)
+                   hs.lights, device, refittable)
+
+    def refit(self, triangles, stream: Optional[int] = None, timing: bool = False):
+        """Move the scene's triangles (rt_scene_refit / rt_scene_refit_device): ``triangles`` holds
+        the P triangles in the order given at creation, as a numpy (P, 18) float32 array (v0, v1,
+        v2, n0, n1, n2) or a torch tensor of that shape on the scene's device, which takes the
+        device path on ``stream`` (a HIP stream handle; default torch's current stream).  The tree
+        and its records stay; every box, edge and normal is rewritten, so every query answers as
+        the reference does on (nodes, refit_aabbs(nodes, triangles), triangles).  The call waits
+        for the scene's own work and returns when the refit is done.  ``timing=True`` returns the
+        HIP-event ms of its launches.  Only for scenes made with ``refittable=True``."""
+        ms = C.c_float(0.0)
+        P = self.num_triangles
+        if type(triangles).__module__.split(".")[0] == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if triangles.device != dev or triangles.dtype != torch.float32 or triangles.numel() != 18 * P:
+                raise ValueError(f"refit: expects a ({P}, 18) float32 tensor on {dev}")
+            t = triangles.contiguous()
+            check(lib().rt_scene_refit_device(self._handle(), t.data_ptr(), _stream_of(stream, dev),
+                                              C.byref(ms) if timing else None))
+        else:
+            t = _c(triangles, np.float32)
+            if t.size != 18 * P:
+                raise ValueError(f"refit: expects a ({P}, 18) array of triangles")
+            check(lib().rt_scene_refit(self._handle(), ptr(t), C.byref(ms) if timing else None))
+        return ms.value if timing else None
+
+    def digest(self) -> tuple:
+        """(info (21,) int64, digests (22,) uint64) of the resident arrays, read back from the
+        device and hashed (rt_debug_scene_digest): rt_debug_scene_pack's words."""
+        info, dig = np.zeros(21, np.int64), np.zeros(22, np.uint64)
+        check(lib().rt_debug_scene_digest(self._handle(), ptr(info), ptr(dig)))
+        return info, dig
 
     @property
     def handle(self) -> C.c_void_p:
@@ -1665,6 +1701,46 @@ def build_bvh(positions, indices):
     aabbs = np.zeros((2 * P - 1, 6), np.float32)
     check(lib().rt_build_bvh(ptr(pos), pos.size // 3, ptr(idx), P, ptr(nodes), ptr(aabbs)))
     return nodes, aabbs
+
+
+def refit_aabbs(nodes, triangles) -> np.ndarray:
+    """The (2P-1, 6) boxes a refit gives the tree ``nodes`` over ``triangles`` (P, 18), on the host
+    (rt_refit_aabbs_host): aabb_of_triangle per leaf, merge(left, right) bottom-up."""
+    nd, tr = _c(nodes, np.uint32), _c(triangles, np.float32)
+    P = tr.size // 18
+    if nd.size != 4 * (2 * P - 1):
+        raise ValueError("refit_aabbs: expects 2P-1 nodes for P triangles")
+    out = np.zeros((2 * P - 1, 6), np.float32)
+    check(lib().rt_refit_aabbs_host(P, ptr(nd), ptr(tr), ptr(out)))
+    return out
+
+
+def triangles_from_mesh(positions, indices, normals=None, device: int = 0, stream=None):
+    """The (P, 18) triangle array of an indexed mesh as a device tensor
+    (rt_triangles_from_mesh_device; G/src/main.cu:388-404: zero normals when the mesh has none).
+    positions (nv, 3) float32, indices (P, 3) uint32 and normals (nv, 3) may be numpy arrays or
+    device tensors; with tensors nothing leaves the GPU, so deformed vertices reach
+    DeviceScene.refit directly."""
+    import torch
+
+    dev = torch.device("cuda", device)
+
+    def on_dev(a, dt_np):
+        if isinstance(a, torch.Tensor):
+            return a.to(dev).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a, dt_np).view(np.int32 if dt_np == np.uint32 else dt_np)
+                                .copy()).to(dev)
+
+    pos = on_dev(positions, np.float32).reshape(-1, 3)
+    idx = on_dev(indices, np.uint32).reshape(-1, 3)
+    nrm = None if normals is None else on_dev(normals, np.float32).reshape(-1, 3)
+    if nrm is not None and nrm.shape[0] != pos.shape[0]:
+        raise ValueError("triangles_from_mesh: one normal per vertex")
+    P = idx.shape[0]
+    tris = torch.empty((P, 18), dtype=torch.float32, device=dev)
+    check(lib().rt_triangles_from_mesh_device(device, pos.data_ptr(), pos.shape[0], None if nrm is None else nrm.data_ptr(),
+                                              idx.data_ptr(), P, tris.data_ptr(), _stream_of(stream, dev)))
+    return tris
 
 
 def build_bvh_device(positions, indices, device: int = 0, stream=None, tensors: bool = False):

@@ -36,6 +36,7 @@
 //   rt_prepass.hpp     tile bounds, root and tree-cut culling passes, work lists
 //   rt_query.hpp       batched ray queries on a resident scene (rt_trace_rays*, rt_shade_rays*)
 //   rt_path.hpp        path stages for caller hits (rt_path_*): step, begin, compaction, finish
+//   rt_refit.hpp       refit of a resident scene for deforming geometry (rt_scene_refit*), mesh -> triangles
 //   rt_scan.hpp        the compaction's scan of tile counts (through rt_path.hpp; also used by rt_frame.hip)
 // Separate translation units: rt_scene_pack.cpp (the host half of rt_scene_create: checks, ids,
 // stack bounds, every packed array), rt_records.cpp (host record builders), rt_hw1.hip (the HW1
@@ -194,6 +195,7 @@ struct RenderParams {
 #include "rt_prepass.hpp"
 #include "rt_query.hpp"
 #include "rt_path.hpp"
+#include "rt_refit.hpp"
 
 // The render kernel's work: list q's entries, its heavy lists' first (classes in order,
 // heaviest first; each capped at heavy_cap), then its survivors (the cut pass's list, or the
@@ -676,6 +678,14 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     DevBuf cut;  // tile culling: boxes of a cut of the tree (6 floats each)
     DevBuf cut2;  // 2^cut_sub_log2 boxes below each cut box (cut_unit's second level), 6 floats each
     DevBuf tri;         // deep: triangles by index (brute-force completion)
+    // rt_scene_create_refittable: the refit plan on the device (rt::RefitPlan; rt_refit.hpp) — the
+    // bottom-up schedule, its level offsets, fnode record -> node, the cut slots' nodes (cut's then
+    // cut2's) — and the finite check's flag word
+    bool refittable = false;
+    DevBuf rf_order, rf_levels, rf_frec, rf_cut, rf_flag;
+    uint32_t rf_n_int = 0, rf_n_leaf = 0, rf_nrec = 0, rf_ncut = 0, rf_ncut2 = 0;
+    std::vector<uint32_t> rf_level_off;  // host copy: the launches per level
+    int binary_stack = 0, wide_stack = 0;  // DFS stack bounds of the records (rt_debug_scene_digest)
     DevBuf work;  // kSets counter sets, then kSets x (live lists | cut survivor lists | heavy lists)
     int64_t last_tiles_total = 0;
     int cus = 256;
@@ -829,11 +839,37 @@ SceneView scene_view(const rt_scene* s) {
     v.fault = static_cast<uint32_t*>(s->fault.p);
     return v;
 }
-}  // namespace
 
-extern "C" int rt_scene_create(int device, size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs,
-                               const rt_triangle* tris, const int32_t* objids, const rt_material* mats,
-                               int nmat, const rt_light* lights, int nlights, rt_scene** out) {
+// The refit plan's device buffers (rt_scene_create_refittable, and rt_scene_clone of such a scene).
+constexpr DevBuf rt_scene::*kRefitBufs[] = {&rt_scene::rf_order, &rt_scene::rf_levels, &rt_scene::rf_frec,
+                                            &rt_scene::rf_cut, &rt_scene::rf_flag};
+
+int upload_words(DevBuf& b, const std::vector<uint32_t>& w) {  // (an empty list keeps one word: no null pointers)
+    const uint32_t none = 0;
+    return w.empty() ? b.upload(&none, sizeof(none)) : b.upload(w.data(), w.size() * sizeof(uint32_t));
+}
+
+int upload_plan(rt_scene* s, const rt::RefitPlan& plan) {
+    s->refittable = true;
+    s->rf_n_int = uint32_t(plan.n_int);
+    s->rf_n_leaf = uint32_t(plan.n_leaf);
+    s->rf_nrec = s->fnode.p ? uint32_t(plan.frec_node.size()) : 0u;
+    s->rf_ncut = s->cut.p ? uint32_t(plan.cut_ref.size()) : 0u;
+    s->rf_ncut2 = s->cut2.p ? uint32_t(plan.cut2_ref.size()) : 0u;
+    s->rf_level_off = plan.level_off;
+    std::vector<uint32_t> cuts(plan.cut_ref.begin(), plan.cut_ref.begin() + s->rf_ncut);
+    cuts.insert(cuts.end(), plan.cut2_ref.begin(), plan.cut2_ref.begin() + s->rf_ncut2);
+    int rc;
+    if ((rc = upload_words(s->rf_order, plan.order)) != RT_OK) return rc;
+    if ((rc = upload_words(s->rf_levels, plan.level_off)) != RT_OK) return rc;
+    if ((rc = upload_words(s->rf_frec, plan.frec_node)) != RT_OK) return rc;
+    if ((rc = upload_words(s->rf_cut, cuts)) != RT_OK) return rc;
+    return upload_words(s->rf_flag, {});
+}
+
+int scene_create(int device, size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                 const int32_t* objids, const rt_material* mats, int nmat, const rt_light* lights, int nlights,
+                 bool refittable, rt_scene** out) {
     if (!out) return set_error(RT_ERR_ARG, "rt_scene_create: null out");
     *out = nullptr;
     int rc = rt::check_scene_arrays(P, nodes, aabbs, tris);
@@ -841,7 +877,8 @@ extern "C" int rt_scene_create(int device, size_t P, const rt_bvh_node* nodes, c
     if (nmat < 0 || nlights < 0 || (nmat > 0 && !mats) || (nlights > 0 && !lights))
         return set_error(RT_ERR_ARG, "rt_scene_create: bad material/light arrays");
     rt::PackedScene pk;
-    if ((rc = rt::pack_scene(P, nodes, aabbs, tris, pk)) != RT_OK) return rc;
+    rt::RefitPlan plan;
+    if ((rc = rt::pack_scene(P, nodes, aabbs, tris, pk, refittable ? &plan : nullptr)) != RT_OK) return rc;
     if ((rc = check_device(device)) != RT_OK) return rc;
     DeviceGuard g(device);
     std::unique_ptr<rt_scene> s(new (std::nothrow) rt_scene());
@@ -850,6 +887,8 @@ extern "C" int rt_scene_create(int device, size_t P, const rt_bvh_node* nodes, c
     s->device = device;
     s->nmat = nmat;
     s->nlights = nlights;
+    s->binary_stack = pk.binary_stack;
+    s->wide_stack = pk.wide_stack;
     size_t i = 0;
     for (const rt::PackedArray& a : pk.arrays()) {
         DevBuf& b = (*s).*kSceneBufs[i++].buf;
@@ -858,11 +897,27 @@ extern "C" int rt_scene_create(int device, size_t P, const rt_bvh_node* nodes, c
     if (objids && (rc = s->objids.upload(objids, P * sizeof(int32_t))) != RT_OK) return rc;
     if (nmat > 0 && (rc = s->mats.upload(mats, size_t(nmat) * sizeof(rt_material))) != RT_OK) return rc;
     if (nlights > 0 && (rc = s->lights.upload(lights, size_t(nlights) * sizeof(rt_light))) != RT_OK) return rc;
+    if (refittable && (rc = upload_plan(s.get(), plan)) != RT_OK) return rc;
     if ((rc = s->create_sync()) != RT_OK) return rc;
     for (const SceneBuf& b : kSceneBufs)
         if (b.counted) s->bytes += ((*s).*b.buf).n;
+    if (refittable)
+        for (DevBuf rt_scene::*b : kRefitBufs) s->bytes += ((*s).*b).n;
     *out = s.release();
     return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_scene_create(int device, size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs,
+                               const rt_triangle* tris, const int32_t* objids, const rt_material* mats,
+                               int nmat, const rt_light* lights, int nlights, rt_scene** out) {
+    return scene_create(device, P, nodes, aabbs, tris, objids, mats, nmat, lights, nlights, false, out);
+}
+
+extern "C" int rt_scene_create_refittable(int device, size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs,
+                                          const rt_triangle* tris, const int32_t* objids, const rt_material* mats,
+                                          int nmat, const rt_light* lights, int nlights, rt_scene** out) {
+    return scene_create(device, P, nodes, aabbs, tris, objids, mats, nmat, lights, nlights, true, out);
 }
 
 extern "C" int rt_scene_clone(const rt_scene* src, int device, rt_scene** out) {
@@ -884,8 +939,185 @@ extern "C" int rt_scene_clone(const rt_scene* src, int device, rt_scene** out) {
         if ((rc = d.alloc(q.n)) != RT_OK) return rc;
         if (q.n) HIP_TRY(hipMemcpyPeer(d.p, device, q.p, src->device, q.n));
     }
+    s->binary_stack = src->binary_stack;
+    s->wide_stack = src->wide_stack;
+    if (src->refittable) {  // the plan with it: a refittable scene's clone is refittable
+        s->refittable = true;
+        s->rf_n_int = src->rf_n_int, s->rf_n_leaf = src->rf_n_leaf, s->rf_nrec = src->rf_nrec;
+        s->rf_ncut = src->rf_ncut, s->rf_ncut2 = src->rf_ncut2;
+        s->rf_level_off = src->rf_level_off;
+        for (DevBuf rt_scene::*b : kRefitBufs) {
+            DevBuf& d = (*s).*b;
+            const DevBuf& q = (*src).*b;
+            if ((rc = d.alloc(q.n)) != RT_OK) return rc;
+            if (q.n) HIP_TRY(hipMemcpyPeer(d.p, device, q.p, src->device, q.n));
+        }
+    }
     if ((rc = s->create_sync()) != RT_OK) return rc;
     *out = s.release();
+    return RT_OK;
+}
+
+// ---- refit (rt_refit.hpp) ------------------------------------------------------------------------
+namespace {
+unsigned refit_grid(size_t n) { return unsigned((n + BLOCK - 1) / BLOCK); }
+
+RefitView refit_view(const rt_scene* s) {
+    RefitView v;
+    std::memset(&v, 0, sizeof(v));
+    v.inode = static_cast<float4*>(s->inode.p);
+    v.wnode = static_cast<float4*>(s->wnode.p);
+    v.fnode = static_cast<float*>(s->fnode.p);
+    v.ibox = static_cast<float4*>(s->ibox.p);
+    v.leaf = static_cast<float4*>(s->leaf.p);
+    v.tnorm = static_cast<float4*>(s->tnorm.p);
+    v.tri = static_cast<float4*>(s->tri.p);
+    v.cut = static_cast<float*>(s->cut.p);
+    v.cut2 = static_cast<float*>(s->cut2.p);
+    v.order = static_cast<const uint32_t*>(s->rf_order.p);
+    v.level_off = static_cast<const uint32_t*>(s->rf_levels.p);
+    v.frec = static_cast<const uint32_t*>(s->rf_frec.p);
+    v.cut_ref = static_cast<const uint32_t*>(s->rf_cut.p);
+    v.n_int = s->rf_n_int;
+    v.n_leaf = s->rf_n_leaf;
+    v.P = uint32_t(s->P);
+    v.root_ref = s->root_ref;
+    v.f_log2 = uint32_t(s->f_log2);
+    v.nrec = s->rf_nrec;
+    v.ncut_slots = s->rf_ncut + s->rf_ncut2;
+    return v;
+}
+}  // namespace
+
+extern "C" int rt_scene_refit_device(rt_scene* s, const rt_triangle* tris_dev, void* hip_stream, float* ms) {
+    if (!s || !tris_dev) return set_error(RT_ERR_ARG, "rt_scene_refit_device: null argument");
+    if (!s->refittable) return set_error(RT_ERR_UNSUPPORTED, "rt_scene_refit_device: the scene was not created refittable");
+    DeviceGuard g(s->device);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // the scene's own streams (pre-passes, overlapped render kernels) and the caller's, before any write
+    HIP_TRY(hipStreamSynchronize(s->prep));
+    for (hipStream_t r : s->rstream) HIP_TRY(hipStreamSynchronize(r));
+    HIP_TRY(hipStreamSynchronize(st));
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } ev;
+    if (ms) {
+        *ms = 0.f;
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, st));
+    }
+    const RefitView v = refit_view(s);
+    const float* tris = reinterpret_cast<const float*>(tris_dev);
+    uint32_t* bad = static_cast<uint32_t*>(s->rf_flag.p);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(refit_check_kernel, dim3(refit_grid(s->P)), dim3(BLOCK), 0, st, tris, v.P, bad);
+    HIP_TRY(hipGetLastError());
+    uint32_t hbad = 0;
+    HIP_TRY(hipMemcpyAsync(&hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hbad) return set_error(RT_ERR_ARG, "rt_scene_refit_device: a vertex coordinate is not finite");
+    hipLaunchKernelGGL(refit_leaves_kernel, dim3(refit_grid(v.n_leaf)), dim3(BLOCK), 0, st, v, tris);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(refit_triangles_kernel, dim3(refit_grid(v.P)), dim3(BLOCK), 0, st, v, tris);
+    HIP_TRY(hipGetLastError());
+    // levels wider than one workgroup launch by launch, the rest (they shrink) in one workgroup
+    const std::vector<uint32_t>& off = s->rf_level_off;
+    const uint32_t levels = uint32_t(off.size()) - 1;
+    uint32_t h = 1;
+    for (; h <= levels && off[h] - off[h - 1] > uint32_t(REFIT_TOP); ++h) {
+        hipLaunchKernelGGL(refit_level_kernel, dim3(refit_grid(off[h] - off[h - 1])), dim3(BLOCK), 0, st, v, off[h - 1],
+                           off[h] - off[h - 1]);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(refit_top_levels_kernel, dim3(1), dim3(REFIT_TOP), 0, st, v, h, levels);
+    HIP_TRY(hipGetLastError());
+    if (v.wnode && v.n_int > 0) {
+        hipLaunchKernelGGL(refit_wnode_kernel, dim3(refit_grid(v.n_int)), dim3(BLOCK), 0, st, v);
+        HIP_TRY(hipGetLastError());
+    }
+    if (v.fnode && v.nrec > 0) {
+        hipLaunchKernelGGL(refit_fnode_kernel, dim3(refit_grid(size_t(v.nrec) << v.f_log2)), dim3(BLOCK), 0, st, v);
+        HIP_TRY(hipGetLastError());
+    }
+    if (v.ncut_slots > 0) {
+        hipLaunchKernelGGL(refit_cut_kernel, dim3(refit_grid(v.ncut_slots)), dim3(BLOCK), 0, st, v, s->rf_ncut);
+        HIP_TRY(hipGetLastError());
+    }
+    if (ms) HIP_TRY(hipEventRecord(ev.b, st));
+    // the root's box (its trailing ibox copy, pairs) back for the host-side root_box and bmax: the
+    // boxes are nested and finite, so the root's |coordinates| bound every box's
+    float rootb[8];
+    const char* rootb_dev = static_cast<const char*>(s->ibox.p) + s->ibox.n - sizeof(rootb);
+    HIP_TRY(hipMemcpyAsync(rootb, rootb_dev, sizeof(rootb), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, ev.a, ev.b));
+    for (int a = 0; a < 3; ++a) {
+        s->root_box[a] = rootb[2 * a];
+        s->root_box[3 + a] = rootb[2 * a + 1];
+        s->bmax[a] = std::max(std::fabs(rootb[2 * a]), std::fabs(rootb[2 * a + 1]));
+    }
+    s->cost_key = 0;  // the per-tile cost history is the old geometry's
+    return RT_OK;
+}
+
+extern "C" int rt_scene_refit(rt_scene* s, const rt_triangle* tris, float* ms) {
+    if (!s || !tris) return set_error(RT_ERR_ARG, "rt_scene_refit: null argument");
+    if (!s->refittable) return set_error(RT_ERR_UNSUPPORTED, "rt_scene_refit: the scene was not created refittable");
+    DeviceGuard g(s->device);
+    DevBuf d;
+    if (int rc = d.upload(tris, s->P * sizeof(rt_triangle)); rc != RT_OK) return rc;
+    return rt_scene_refit_device(s, static_cast<const rt_triangle*>(d.p), nullptr, ms);
+}
+
+extern "C" int rt_triangles_from_mesh_device(int device, const rt_vec3* positions_dev, size_t num_vertices,
+                                             const rt_vec3* normals_dev, const uint32_t* indices_dev, size_t P,
+                                             rt_triangle* tris_dev, void* hip_stream) {
+    if (!positions_dev || !indices_dev || !tris_dev)
+        return set_error(RT_ERR_ARG, "rt_triangles_from_mesh_device: null argument");
+    if (P == 0) return set_error(RT_ERR_ARG, "no triangles");
+    if (P > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^31-1 triangles");
+    if (num_vertices > 0xFFFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^32-1 vertices");
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    DeviceGuard g(device);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    uint32_t* err = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&err), sizeof(uint32_t), st));
+    struct Free {
+        void* p; hipStream_t s;
+        ~Free() { (void)hipFreeAsync(p, s); }
+    } free_err{err, st};
+    HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(mesh_triangles_kernel, dim3(refit_grid(P)), dim3(BLOCK), 0, st,
+                       reinterpret_cast<const float*>(positions_dev), reinterpret_cast<const float*>(normals_dev),
+                       uint32_t(num_vertices), indices_dev, uint32_t(P), reinterpret_cast<float*>(tris_dev), err);
+    HIP_TRY(hipGetLastError());
+    uint32_t herr = 0;
+    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (herr) return set_error(RT_ERR_ARG, "triangle index out of range");
+    return RT_OK;
+}
+
+// rt_debug_scene_pack's view of a resident scene: the packed arrays read back and hashed.
+extern "C" int rt_debug_scene_digest(rt_scene* s, int64_t info[21], uint64_t digests[22]) {
+    if (!s || !info || !digests) return set_error(RT_ERR_ARG, "rt_debug_scene_digest: null argument");
+    DeviceGuard g(s->device);
+    HIP_TRY(hipDeviceSynchronize());
+    rt::scene_info_words(*s, s->binary_stack, s->wide_stack, info);
+    std::vector<uint8_t> host;
+    for (size_t i = 0; i < rt::PackedScene::kArrays; ++i) {
+        const DevBuf& b = (*s).*kSceneBufs[i].buf;
+        host.resize(b.n);
+        if (b.n) HIP_TRY(hipMemcpy(host.data(), b.p, b.n, hipMemcpyDeviceToHost));
+        digests[2 * i] = b.n;
+        digests[2 * i + 1] = rt::fnv1a(host.data(), b.n);
+    }
     return RT_OK;
 }
 

@@ -705,24 +705,7 @@ bool file_exists(const std::string& p) { std::ifstream f(p); return bool(f); }
 // ---------------------------------------------------------------------------------------
 namespace {
 
-inline rt_aabb aabb_empty() {
-    return rt_aabb{v3(INFINITY, INFINITY, INFINITY), v3(-INFINITY, -INFINITY, -INFINITY)};
-}
-inline rt_aabb aabb_merge(const rt_aabb& a, const rt_aabb& b) {
-    return rt_aabb{v3(fminf(a.min_corner.x, b.min_corner.x), fminf(a.min_corner.y, b.min_corner.y),
-                      fminf(a.min_corner.z, b.min_corner.z)),
-                   v3(fmaxf(a.max_corner.x, b.max_corner.x), fmaxf(a.max_corner.y, b.max_corner.y),
-                      fmaxf(a.max_corner.z, b.max_corner.z))};
-}
-inline rt_aabb aabb_of_triangle(rt_vec3 a, rt_vec3 b, rt_vec3 c) {
-    rt_aabb box;
-    box.min_corner = v3(fminf(a.x, fminf(b.x, c.x)), fminf(a.y, fminf(b.y, c.y)), fminf(a.z, fminf(b.z, c.z)));
-    box.max_corner = v3(fmaxf(a.x, fmaxf(b.x, c.x)), fmaxf(a.y, fmaxf(b.y, c.y)), fmaxf(a.z, fmaxf(b.z, c.z)));
-    const float eps = 0.0f;
-    box.min_corner = v3(box.min_corner.x - eps, box.min_corner.y - eps, box.min_corner.z - eps);
-    box.max_corner = v3(box.max_corner.x + eps, box.max_corner.y + eps, box.max_corner.z + eps);
-    return box;
-}
+// aabb_empty, aabb_merge, aabb_of_triangle: rt_common.hpp (shared with the refit, rt_scene_pack.cpp)
 inline uint32_t bit_expansion(uint32_t v) {
     v = (v * 0x00010001u) & 0xFF0000FFu;
     v = (v * 0x00000101u) & 0x0F00F00Fu;

@@ -69,7 +69,7 @@ double box_weight(const rt_aabb& b, int rule, uint32_t leaves) {
 }
 
 FrustumRecords build_frustum_records(const rt_bvh_node* nodes, size_t NN, const uint32_t* cid,
-                                     const rt_aabb* aabbs, int dmax, int cap) {
+                                     const rt_aabb* aabbs, int dmax, int cap, std::vector<uint32_t>* rec_nodes) {
     FrustumRecords out;
     auto ref_of0 = [&](uint32_t n) -> uint32_t { return n == NO_REF ? NO_REF : cid[n]; };
     // RT_TUNE_RECORD_GREEDY: a record's entries are grown from its node's children by expanding,
@@ -146,6 +146,7 @@ FrustumRecords build_frustum_records(const rt_bvh_node* nodes, size_t NN, const 
         out.log2 = D;
         out.bound = SF[0];
         out.nrec = recs.size();
+        if (rec_nodes) *rec_nodes = std::move(recs);
         return out;
     }
     return out;

@@ -36,8 +36,10 @@ std::vector<uint32_t> subtree_leaves(const rt_bvh_node* nodes, size_t NN, const 
 // times by rule 2 sqrt(leaves), 3 log2(leaves + 1), 4 leaves; 1e300 when that is not finite.
 double box_weight(const rt_aabb& b, int rule, uint32_t leaves);
 // The largest-arity frustum records (2^3..2^dmax) whose DFS fits `cap` stack entries.
+// rec_nodes (optional): the binary node each record expands, by record index (the refit plan).
 FrustumRecords build_frustum_records(const rt_bvh_node* nodes, size_t NN, const uint32_t* cid,
-                                     const rt_aabb* aabbs, int dmax, int cap);
+                                     const rt_aabb* aabbs, int dmax, int cap,
+                                     std::vector<uint32_t>* rec_nodes = nullptr);
 // The records quantised (16-bit grid steps per entry); false when they cannot be.
 bool build_quant_records(const FrustumRecords& fr, std::vector<uint32_t>& qent, std::vector<float>& qhdr);
 

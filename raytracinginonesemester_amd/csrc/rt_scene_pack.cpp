@@ -241,7 +241,7 @@ void pack_bounds(const Tree& t, PackedScene& out) {
 // inside each cut node's subtree, so the tiles whose rays reach a cut box are tested against the
 // boxes below it (cut_unit).  Unused slots repeat the node's first sub-box: a duplicate
 // changes no "every box missed" decision.
-void pack_cut(const Tree& t, PackedScene& out) {
+void pack_cut(const Tree& t, PackedScene& out, RefitPlan* plan) {
     if (t.cid[0] == NO_REF || (t.cid[0] & LEAF_BIT)) return;
     const int kcut = int(std::clamp(tuning(RT_TUNE_CULL_BOXES, 64.0), 0.0, 64.0));
     auto area = [&](uint32_t n) {  // not clamped: a box with a negative area is never replaced
@@ -256,6 +256,8 @@ void pack_cut(const Tree& t, PackedScene& out) {
     if (kcut <= 1) return;
     out.cut.resize(size_t(6) * ncut);
     for (int i = 0; i < ncut; ++i) put_corners(&out.cut[6 * i], t.aabbs[cutn[i]]);
+    if (plan)
+        for (int i = 0; i < ncut; ++i) plan->cut_ref.push_back(t.cid[cutn[i]]);
     out.meta.ncut = ncut;
     const int sub = int(std::clamp(tuning(RT_TUNE_CUT_SUB, 16.0), 0.0, 64.0));
     if (sub < 2) return;
@@ -268,13 +270,15 @@ void pack_cut(const Tree& t, PackedScene& out) {
         int ns = expand_largest(t.nodes, t.cid, sn, 1, S, false, area);
         if (ns == 0) sn[ns++] = cutn[i];  // (an internal node without valid children)
         for (int j = 0; j < S; ++j) put_corners(&out.cut2[6 * (size_t(i) * S + j)], t.aabbs[sn[j < ns ? j : 0]]);
+        if (plan)
+            for (int j = 0; j < S; ++j) plan->cut2_ref.push_back(t.cid[sn[j < ns ? j : 0]]);
     }
     out.meta.cut_sub_log2 = sl;
 }
 
 // The camera rays' frustum records (build_frustum_records), for the traversal's 128-entry
 // stack, and their quantised form.
-void pack_frustum(const Tree& t, PackedScene& out) {
+void pack_frustum(const Tree& t, PackedScene& out, RefitPlan* plan) {
     // RT_TUNE_FRUSTUM_ARITY: the largest arity's log2 to try (tests; 2 = the 4-ary records)
     int fr_dmax = int(std::clamp(tuning(RT_TUNE_FRUSTUM_ARITY, 5.0), 2.0, 5.0));
 #ifdef RT_NO_F16  // (variant builds for A/B runs: the frustum traversal over the 4-ary records)
@@ -284,8 +288,11 @@ void pack_frustum(const Tree& t, PackedScene& out) {
     // RT_TUNE_FRUSTUM_STACK_CAP (test hook only): records whose DFS may outgrow the stack,
     // to exercise traverse_frustum's overflow guard
     const int cap = int(std::clamp(tuning(RT_TUNE_FRUSTUM_STACK_CAP, double(FRUSTUM_STACK)), 1.0, 1e6));
-    FrustumRecords fr = build_frustum_records(t.nodes, t.NN, t.cid, t.aabbs, fr_dmax, cap);
+    std::vector<uint32_t> rec_nodes;
+    FrustumRecords fr = build_frustum_records(t.nodes, t.NN, t.cid, t.aabbs, fr_dmax, cap, plan ? &rec_nodes : nullptr);
     if (fr.log2 <= 2) return;
+    if (plan)
+        for (const uint32_t n : rec_nodes) plan->frec_node.push_back(t.cid[n]);
     out.meta.f_log2 = fr.log2;
     out.meta.f_bound = fr.bound;
     // RT_TUNE_QUANT_RECORDS: 1 quantised records for every scene with frustum records,
@@ -328,7 +335,68 @@ int classify_nodes(size_t P, const rt_bvh_node* nodes, NodeIds& ids) {
     return RT_OK;
 }
 
-int pack_scene(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris, PackedScene& out) {
+int check_proper_tree(size_t P, const rt_bvh_node* nodes, std::vector<uint32_t>* height) {
+    const size_t NN = 2 * P - 1;
+    std::vector<uint8_t> state(NN, 0);  // 0 new, 1 on path, 2 done
+    std::vector<uint32_t> H(NN, 0u);
+    std::vector<std::pair<uint32_t, bool>> st{{0u, false}};
+    size_t reached = 0;
+    while (!st.empty()) {
+        auto [v, post] = st.back();
+        st.pop_back();
+        const rt_bvh_node& nd = nodes[v];
+        const bool internal = nd.object_idx == 0xFFFFFFFFu;
+        if (post) {
+            state[v] = 2;
+            H[v] = 1 + std::max(H[nd.left_idx], H[nd.right_idx]);
+            continue;
+        }
+        if (state[v] == 1) return set_error(RT_ERR_ARG, "BVH contains a cycle");
+        if (state[v] == 2) return set_error(RT_ERR_UNSUPPORTED, "refit: a node has two parents");
+        ++reached;
+        if (!internal) {
+            if (nd.object_idx >= P) return set_error(RT_ERR_UNSUPPORTED, "refit: a leaf names no triangle");
+            state[v] = 2;
+            continue;
+        }
+        if (nd.left_idx == NO_REF || nd.right_idx == NO_REF)
+            return set_error(RT_ERR_UNSUPPORTED, "refit: an internal node lacks a child");
+        if (nd.left_idx >= NN || nd.right_idx >= NN) return set_error(RT_ERR_ARG, "BVH child index out of range");
+        state[v] = 1;
+        st.push_back({v, true});
+        st.push_back({nd.left_idx, false});
+        st.push_back({nd.right_idx, false});
+    }
+    if (reached != NN) return set_error(RT_ERR_UNSUPPORTED, "refit: a node is not reachable from the root");
+    if (height) *height = std::move(H);
+    return RT_OK;
+}
+
+namespace {
+
+// The bottom-up schedule of a proper tree: its internal nodes' compact ids by height.
+int plan_schedule(const Tree& t, const NodeIds& ids, RefitPlan& plan) {
+    std::vector<uint32_t> height;
+    if (int rc = check_proper_tree(t.P, t.nodes, &height); rc != RT_OK) return rc;
+    plan.n_int = ids.n_int;
+    plan.n_leaf = ids.n_leaf;
+    const uint32_t top = height[0];
+    std::vector<uint32_t> count(size_t(top) + 1, 0u);
+    for (size_t n = 0; n < t.NN; ++n)
+        if (height[n] > 0) ++count[height[n]];
+    plan.level_off.assign(size_t(top) + 1, 0u);  // level_off[h]: the end of level h (level_off[0] = 0)
+    for (uint32_t h = 1; h <= top; ++h) plan.level_off[h] = plan.level_off[h - 1] + count[h];
+    plan.order.assign(ids.n_int, 0u);
+    std::vector<uint32_t> at(plan.level_off.begin(), plan.level_off.end());
+    for (size_t n = 0; n < t.NN; ++n)  // array order is compact-id order
+        if (height[n] > 0) plan.order[at[height[n] - 1]++] = t.cid[n];
+    return RT_OK;
+}
+
+}  // namespace
+
+int pack_scene(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris, PackedScene& out,
+               RefitPlan* plan) {
     int rc = check_scene_arrays(P, nodes, aabbs, tris);
     if (rc != RT_OK) return rc;
     out = PackedScene();
@@ -338,6 +406,10 @@ int pack_scene(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const r
     const WideRule w(t);
     StackBounds sb;
     if ((rc = stack_bounds(t, w, sb)) != RT_OK) return rc;
+    if (plan) {
+        *plan = RefitPlan();
+        if ((rc = plan_schedule(t, ids, *plan)) != RT_OK) return rc;
+    }
     // A tree whose DFS may need more than the 64-entry wave stack is rendered by the MODE_DEEP
     // kernels (the reference's 512-entry stack).  traverse_wave_split addresses records by 32-bit
     // byte offsets (ref << 7 into the 4-ary array, << 5 into ibox, slot << 6 into the leaves):
@@ -350,14 +422,116 @@ int pack_scene(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const r
     out.wide_stack = sb.wide;
     pack_records(t, ids, tris, w, wide_ok, out);
     pack_bounds(t, out);
-    pack_cut(t, out);
+    pack_cut(t, out, plan);
     m.wide = wide_ok && !(m.root_ref & LEAF_BIT);
     m.lane_stack = !deep && sb.binary <= LANE_LDS_CAP;
     m.lane_wide = m.wide && m.lane_stack && sb.wide <= LANE_LDS_CAP;
     m.deep = deep;
-    if (m.wide) pack_frustum(t, out);
+    if (m.wide) pack_frustum(t, out, plan);
     if (deep) pack_triangles(P, tris, out.tri);
+    if (plan && !out.qent.empty())  // (their grids are per record: a refit would have to re-quantise)
+        return set_error(RT_ERR_UNSUPPORTED, "refit: quantised records (RT_TUNE_QUANT_RECORDS) are not refitted");
     return RT_OK;
+}
+
+namespace {
+
+uint32_t word(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+}
+
+// A node's current box in the packed arrays, per axis (min, max): an internal node's ibox entry, a
+// leaf's record words 10-15.
+const float* box_of(const PackedScene& pk, uint32_t ref) {
+    return ref & LEAF_BIT ? &pk.leaf[16 * size_t(ref & ~LEAF_BIT) + 10] : &pk.ibox[8 * size_t(ref)];
+}
+void pairs_to_corners(float* q, const float* b) { put4(q, b[0], b[2], b[4], b[1]), q[4] = b[3], q[5] = b[5]; }
+
+bool finite_vertices(size_t P, const rt_triangle* tris) {
+    for (size_t i = 0; i < P; ++i)
+        for (const rt_vec3& v : {tris[i].v0, tris[i].v1, tris[i].v2})
+            if (!std::isfinite(v.x) || !std::isfinite(v.y) || !std::isfinite(v.z)) return false;
+    return true;
+}
+
+}  // namespace
+
+int refit_packed(PackedScene& pk, const RefitPlan& plan, const rt_triangle* tris) {
+    const size_t P = pk.meta.P;
+    if (!tris) return set_error(RT_ERR_ARG, "refit: null triangles");
+    if (!finite_vertices(P, tris)) return set_error(RT_ERR_ARG, "refit: a vertex coordinate is not finite");
+    // 1, 2: the leaves' boxes and v0 | e1 | e2 (pack_records), tnorm, tri (pack_triangles)
+    for (size_t j = 0; j < plan.n_leaf; ++j) {
+        float* q = &pk.leaf[16 * j];
+        const rt_triangle& tr = tris[word(q[3])];
+        const float tif = q[3];
+        put4(q, tr.v0.x, tr.v0.y, tr.v0.z, tif);
+        put4(q + 4, tr.v1.x - tr.v0.x, tr.v1.y - tr.v0.y, tr.v1.z - tr.v0.z, tr.v2.x - tr.v0.x);
+        q[8] = tr.v2.y - tr.v0.y, q[9] = tr.v2.z - tr.v0.z;
+        put_pairs(q + 10, aabb_of_triangle(tr.v0, tr.v1, tr.v2));
+    }
+    for (size_t i = 0; i < P; ++i) {
+        float* q = &pk.tnorm[12 * i];
+        put4(q, tris[i].n0.x, tris[i].n0.y, tris[i].n0.z, 0.f);
+        put4(q + 4, tris[i].n1.x, tris[i].n1.y, tris[i].n1.z, 0.f);
+        put4(q + 8, tris[i].n2.x, tris[i].n2.y, tris[i].n2.z, 0.f);
+    }
+    if (!pk.tri.empty()) pack_triangles(P, tris, pk.tri);
+    // 3: internal boxes bottom-up, merge(left, right); with them the inode child boxes
+    for (const uint32_t i : plan.order) {
+        float* q = &pk.inode[16 * size_t(i)];
+        const float* l = box_of(pk, word(q[12]));
+        const float* r = box_of(pk, word(q[13]));
+        float m[6];
+        for (int k = 0; k < 6; k += 2) m[k] = fminf(l[k], r[k]), m[k + 1] = fmaxf(l[k + 1], r[k + 1]);
+        std::copy(l, l + 6, q);
+        std::copy(r, r + 6, q + 6);
+        std::copy(m, m + 6, &pk.ibox[8 * size_t(i)]);
+    }
+    // 4: every other stored box from its node
+    const float* root = box_of(pk, pk.meta.root_ref);
+    std::copy(root, root + 6, &pk.ibox[8 * std::max<size_t>(plan.n_int, 1)]);
+    for (size_t i = 0; i < (pk.wnode.empty() ? 0 : plan.n_int); ++i) {
+        float* wq = &pk.wnode[32 * i];
+        for (int e = 0; e < 4; ++e)
+            if (word(wq[24 + e]) != NO_REF) std::copy_n(box_of(pk, word(wq[24 + e])), 6, wq + 6 * e);
+    }
+    const size_t A = size_t(1) << pk.meta.f_log2;
+    for (size_t r = 0; r < (pk.fnode.empty() ? 0 : plan.frec_node.size()); ++r) {
+        float* w = &pk.fnode[8 * A * r];
+        for (size_t i = 0; i < A; ++i) {
+            const uint32_t ref = word(w[6 * A + i]);
+            if (ref == NO_REF) continue;
+            std::copy_n(box_of(pk, ref & LEAF_BIT ? ref : plan.frec_node[ref]), 6, w + 6 * i);
+        }
+    }
+    for (size_t s = 0; s < plan.cut_ref.size() && 6 * s < pk.cut.size(); ++s)
+        pairs_to_corners(&pk.cut[6 * s], box_of(pk, plan.cut_ref[s]));
+    for (size_t s = 0; s < plan.cut2_ref.size() && 6 * s < pk.cut2.size(); ++s)
+        pairs_to_corners(&pk.cut2[6 * s], box_of(pk, plan.cut2_ref[s]));
+    // root_box, and bmax: the boxes are nested and finite, so the root's |coordinates| bound them all
+    SceneMeta& m = pk.meta;
+    pairs_to_corners(m.root_box, root);
+    for (int a = 0; a < 3; ++a) m.bmax[a] = std::max(std::fabs(root[2 * a]), std::fabs(root[2 * a + 1]));
+    return RT_OK;
+}
+
+void scene_info_words(const SceneMeta& m, int binary_stack, int wide_stack, int64_t info[21]) {
+    const int64_t facts[12] = {int64_t(m.P), m.root_ref,  m.ncut, m.cut_sub_log2, m.wide,       m.lane_stack,
+                               m.lane_wide,  m.deep,      m.f_log2, m.f_bound,    binary_stack, wide_stack};
+    std::copy(facts, facts + 12, info);
+    uint32_t bits[9];
+    std::memcpy(bits, m.root_box, sizeof(m.root_box));
+    std::memcpy(bits + 6, m.bmax, sizeof(m.bmax));
+    std::copy(bits, bits + 9, info + 12);
+}
+
+uint64_t fnv1a(const void* data, size_t bytes) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t b = 0; b < bytes; ++b) h = (h ^ static_cast<const uint8_t*>(data)[b]) * 0x100000001b3ull;
+    return h;
 }
 
 }  // namespace rt
@@ -392,6 +566,15 @@ extern "C" int rt_debug_frustum_records(size_t P, const rt_bvh_node* nodes, cons
     return RT_OK;
 }
 
+static void digest_pack(const rt::PackedScene& pk, int64_t info[21], uint64_t digests[22]) {
+    rt::scene_info_words(pk.meta, pk.binary_stack, pk.wide_stack, info);
+    size_t i = 0;
+    for (const rt::PackedArray& a : pk.arrays()) {
+        digests[i++] = a.bytes;
+        digests[i++] = rt::fnv1a(a.data, a.bytes);
+    }
+}
+
 // pack_scene on the host for the CPU tests (no device).  info: P, root_ref, ncut, cut_sub_log2,
 // wide, lane_stack, lane_wide, deep, f_log2, f_bound, binary stack bound, 4-ary stack bound, then
 // the bit patterns of root_box[6] and bmax[3]; digests: per array of PackedScene::arrays(), its
@@ -402,20 +585,49 @@ extern "C" int rt_debug_scene_pack(size_t P, const rt_bvh_node* nodes, const rt_
     rt::PackedScene pk;
     const int rc = rt::pack_scene(P, nodes, aabbs, tris, pk);
     if (rc != RT_OK) return rc;
-    const rt::SceneMeta& m = pk.meta;
-    const int64_t facts[12] = {int64_t(m.P), m.root_ref,  m.ncut, m.cut_sub_log2, m.wide,          m.lane_stack,
-                               m.lane_wide,  m.deep,      m.f_log2, m.f_bound,    pk.binary_stack, pk.wide_stack};
-    std::copy(facts, facts + 12, info);
-    uint32_t bits[9];
-    std::memcpy(bits, m.root_box, sizeof(m.root_box));
-    std::memcpy(bits + 6, m.bmax, sizeof(m.bmax));
-    std::copy(bits, bits + 9, info + 12);
-    size_t i = 0;
-    for (const rt::PackedArray& a : pk.arrays()) {
-        uint64_t h = 0xcbf29ce484222325ull;
-        for (size_t b = 0; b < a.bytes; ++b) h = (h ^ static_cast<const uint8_t*>(a.data)[b]) * 0x100000001b3ull;
-        digests[i++] = a.bytes;
-        digests[i++] = h;
+    digest_pack(pk, info, digests);
+    return RT_OK;
+}
+
+// pack_scene on (nodes, aabbs, tris), then rt::refit_packed with new_tris: the host restatement of
+// rt_scene_create_refittable + rt_scene_refit, in rt_debug_scene_pack's words.
+extern "C" int rt_debug_scene_refit_pack(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                                         const rt_triangle* new_tris, int64_t info[21], uint64_t digests[22]) {
+    return rt_debug_scene_refit_chain(P, nodes, aabbs, tris, 1, &new_tris, info, digests);
+}
+
+// ... with n refits in turn (poses[0], then poses[1], ...).
+extern "C" int rt_debug_scene_refit_chain(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                                          int n, const rt_triangle* const* poses, int64_t info[21], uint64_t digests[22]) {
+    if (!info || !digests || !poses || n < 0) return set_error(RT_ERR_ARG, "rt_debug_scene_refit_chain: bad argument");
+    rt::PackedScene pk;
+    rt::RefitPlan plan;
+    int rc = rt::pack_scene(P, nodes, aabbs, tris, pk, &plan);
+    if (rc != RT_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if ((rc = rt::refit_packed(pk, plan, poses[i])) != RT_OK) return rc;
+    digest_pack(pk, info, digests);
+    return RT_OK;
+}
+
+// The boxes a refit gives the caller's tree, by node: aabb_of_triangle per leaf, merge(left, right)
+// bottom-up.  RT_ERR_UNSUPPORTED unless the tree is proper (rt_scene_create_refittable's rule).
+extern "C" int rt_refit_aabbs_host(size_t P, const rt_bvh_node* nodes, const rt_triangle* tris, rt_aabb* aabbs_out) {
+    int rc = rt::check_scene_arrays(P, nodes, aabbs_out, tris);
+    if (rc != RT_OK) return rc;
+    std::vector<uint32_t> height;
+    if ((rc = rt::check_proper_tree(P, nodes, &height)) != RT_OK) return rc;
+    const size_t NN = 2 * P - 1;
+    std::vector<uint32_t> order;  // internal nodes by height: children before parents
+    for (size_t n = 0; n < NN; ++n) {
+        if (height[n] > 0) {
+            order.push_back(uint32_t(n));
+            continue;
+        }
+        const rt_triangle& tr = tris[nodes[n].object_idx];
+        aabbs_out[n] = rt::aabb_of_triangle(tr.v0, tr.v1, tr.v2);
     }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return height[a] < height[b]; });
+    for (const uint32_t n : order) aabbs_out[n] = rt::aabb_merge(aabbs_out[nodes[n].left_idx], aabbs_out[nodes[n].right_idx]);
     return RT_OK;
 }

@@ -58,11 +58,43 @@ struct NodeIds {
     size_t n_int = 0, n_leaf = 0;
 };
 
+// What a refit of the packed arrays needs beside them.  Every stored box is the
+// box of one tree node; the arrays already hold the topology in compact refs (child refs in
+// inode words 12-13, the triangle index in leaf word 3, entry refs in wnode and fnode), and a
+// node's current box is its ibox entry or its leaf record's words 10-15.  The plan adds the
+// bottom-up schedule and the ref behind each box slot that has none in the arrays.
+struct RefitPlan {
+    size_t n_int = 0, n_leaf = 0;
+    // internal nodes (compact ids) by ascending height, ties by id: level h (leaves are 0) is
+    // order[level_off[h - 1], level_off[h]); a node's children sit in lower levels, and the
+    // levels shrink towards the root
+    std::vector<uint32_t> order, level_off;
+    std::vector<uint32_t> frec_node;          // fnode record -> the internal node it expands
+    std::vector<uint32_t> cut_ref, cut2_ref;  // the node (compact ref) of every cut / cut2 slot
+};
+
 // RT_ERR_ARG for an empty scene, RT_ERR_UNSUPPORTED past 2^30 triangles.
 int check_scene_arrays(size_t P, const void* nodes, const void* aabbs, const void* tris);
 // The ids, after checking every internal node's children against the array (RT_ERR_ARG).
 int classify_nodes(size_t P, const rt_bvh_node* nodes, NodeIds& ids);
 // Everything rt_scene_create derives from the caller's arrays; RT_OK or the error it reports.
-int pack_scene(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris, PackedScene& out);
+// plan (optional): also what a refit needs; RT_ERR_UNSUPPORTED then unless the tree is proper
+// (check_proper_tree) and the records are not quantised.
+int pack_scene(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris, PackedScene& out,
+               RefitPlan* plan = nullptr);
+
+// A tree a refit can keep: every one of the 2P-1 nodes reached from node 0, once; every internal
+// node with two children; every leaf naming a triangle.  RT_ERR_UNSUPPORTED otherwise (RT_ERR_ARG
+// for a child past the array or a cycle).  height (optional): per node, leaves 0.
+int check_proper_tree(size_t P, const rt_bvh_node* nodes, std::vector<uint32_t>* height);
+
+// The host restatement of rt_scene_refit_device: new leaf boxes (aabb_of_triangle) and v0 | e1 | e2,
+// tnorm (and tri), internal boxes merged bottom-up, then every stored box rewritten from its node,
+// root_box and bmax.  RT_ERR_ARG, touching nothing, when a vertex coordinate is not finite.
+int refit_packed(PackedScene& pk, const RefitPlan& plan, const rt_triangle* tris);
+
+// rt_debug_scene_pack's words: the facts as info[21], and the FNV-1a hash of an array's bytes.
+void scene_info_words(const SceneMeta& m, int binary_stack, int wide_stack, int64_t info[21]);
+uint64_t fnv1a(const void* data, size_t bytes);
 
 }  // namespace rt
