@@ -48,7 +48,9 @@ extern "C" {
                                  rt_scene_create_refittable, rt_scene_refit_device, rt_scene_refit,
                                  rt_refit_aabbs_host, rt_triangles_from_mesh_device,
                                  rt_debug_scene_digest, rt_debug_scene_refit_pack,
-                                 rt_debug_scene_refit_chain */
+                                 rt_debug_scene_refit_chain; rt_scene_rebuild_device, rt_scene_rebuild,
+                                 rt_scene_rebuild_path (RT_REBUILD_*), rt_scene_rebuild_counts, rt_build_bvh_triangles,
+                                 rt_debug_box_weight_host, rt_debug_box_weight_batch */
 
 enum {
     RT_OK = 0,
@@ -242,6 +244,42 @@ int rt_refit_aabbs_host(size_t num_triangles, const rt_bvh_node* nodes, const rt
 int rt_triangles_from_mesh_device(int device, const rt_vec3* positions_dev, size_t num_vertices,
                                   const rt_vec3* normals_dev, const uint32_t* indices_dev, size_t num_triangles,
                                   rt_triangle* tris_dev, void* hip_stream);
+
+/* ---- rebuild: new triangles AND a new tree under a resident scene ------------ */
+/* tris_dev: P triangles on the scene's device, in the order given at creation (object ids,
+ * materials and lights stay).  The tree is the reference's LBVH over them: rt_build_bvh over the 3P
+ * vertices v0, v1, v2 of each triangle with indices 0..3P-1 (rt_build_bvh_triangles), built on the
+ * device.  Every packed array, every fact the launches choose kernels by and the refit plan are what
+ * rt_scene_create_refittable makes from (that tree, tris), byte for byte, so every frame and query
+ * answers as on a scene created from them, and the rebuilt scene (and its clone) can be refitted
+ * and rebuilt again.  nodes_out_dev / aabbs_out_dev (optional, 2P-1 each): the tree.
+ * Only scenes created refittable (RT_ERR_UNSUPPORTED otherwise, and when quantised records are in
+ * force).  A first pass checks every vertex coordinate: RT_ERR_ARG if one is not finite.  The call
+ * builds into fresh buffers and swaps them in after everything has succeeded: any error leaves
+ * the scene, its digest and its answers as they were.  After the swap rt_scene_device_bytes
+ * reflects the new sizes and the per-tile cost history is dropped.  Streams as the refit: the call
+ * waits for the scene's own streams and for hip_stream before it works, runs on hip_stream and
+ * synchronises it before returning.  *ms (optional): the HIP-event time from the finite check to the
+ * last launch of the pack (the host path's host work included in the span).
+ * Two paths inside the call, the same bytes from both (rt_scene_rebuild_path says which ran):
+ * RT_REBUILD_DEVICE packs the records on the device too; it handles what the LBVH over finite
+ * triangles gives at the default record rules (P >= 2, nested boxes, a tree that is not deep, a
+ * 4-ary stack within the cap) and honours RT_TUNE_FRUSTUM_ARITY, RT_TUNE_FRUSTUM_STACK_CAP,
+ * RT_TUNE_CULL_BOXES and RT_TUNE_CUT_SUB.  RT_REBUILD_HOST downloads the device-built tree, runs the
+ * host pack with a plan and uploads the result: P == 1, RT_TUNE_RECORD_GREEDY != 2,
+ * RT_TUNE_WIDE4_GREEDY != 1, a deep tree, and quantised records (which it refuses). */
+int rt_scene_rebuild_device(rt_scene* s, const rt_triangle* tris_dev, void* hip_stream,
+                            rt_bvh_node* nodes_out_dev, rt_aabb* aabbs_out_dev, float* ms);
+/* The same from host memory (nodes_out / aabbs_out: host arrays). */
+int rt_scene_rebuild(rt_scene* s, const rt_triangle* tris_host, rt_bvh_node* nodes_out, rt_aabb* aabbs_out, float* ms);
+/* The tree a rebuild gives, on the host: rt_build_bvh over the flattened vertices.  Its internal
+ * nodes are [0, P-1), its leaves [P-1, 2P-1). */
+int rt_build_bvh_triangles(size_t num_triangles, const rt_triangle* tris, rt_bvh_node* nodes, rt_aabb* aabbs);
+enum { RT_REBUILD_NONE = 0, RT_REBUILD_DEVICE = 1, RT_REBUILD_HOST = 2 };
+int rt_scene_rebuild_path(const rt_scene* s);   /* which path the latest rebuild of s took */
+/* counts[0]: kernel launches of the latest rebuild's pack on the device (the tree build's are not
+ * counted), counts[1]: its host read-backs (the host path: 0 and 3).  For measurements. */
+int rt_scene_rebuild_counts(const rt_scene* s, int64_t counts[2]);
 
 enum {
     RT_KERNEL_AUTO = 0,      /* the fastest parity-equivalent kernel */
@@ -915,6 +953,13 @@ int rt_afilm_host(int width, int height, float* sum, uint32_t* count, float* mom
  * over n (x, y) pairs.  Exposed so both can be pinned against the C library's powf. */
 float rt_powf_host(float x, float y);
 int rt_powf_batch(int device, const float* x, const float* y, int n, float* out);
+
+/* The greedy record rules' weight of a box (csrc/rt_records.hpp box_weight: half surface area in
+ * double, rule 2 times sqrt(leaves), 1e300 when not finite) for n boxes (min corner, max corner)
+ * and leaf counts: the host build, and the device build (rules 1 and 2), which a record builder on
+ * the device would have to match bit for bit — the host's sqrt is correctly rounded. */
+int rt_debug_box_weight_host(const float* boxes, const uint32_t* leaves, int rule, int n, double* out);
+int rt_debug_box_weight_batch(int device, const float* boxes, const uint32_t* leaves, int rule, int n, double* out);
 
 /* Host build of the kernels' AABB test for n (ray, box, [tmin,tmax]) triples: out_exact =
  * the reference's double slab test (bvh.h:81-129), out_fast = the float-pre-classified test

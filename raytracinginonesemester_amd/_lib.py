@@ -29,6 +29,7 @@ RT_TIME_GATHER, RT_TIME_DELIVER, RT_TIME_FRAME = 0, 1, 2
 RT_FAULT_FRUSTUM_STACK = 1
 RT_RAYS_CLOSEST, RT_RAYS_OCCLUDED = 0, 1
 RT_RAYS_VARIANT_NONE, RT_RAYS_VARIANT_WIDE, RT_RAYS_VARIANT_BINARY, RT_RAYS_VARIANT_DEEP = 0, 1, 2, 3
+RT_REBUILD_NONE, RT_REBUILD_DEVICE, RT_REBUILD_HOST = 0, 1, 2
 RT_PATH_LAST = 16
 RT_PATH_NONE = 0xFFFFFFFF
 RT_PIXEL_NONE = 0xFFFFFFFF
@@ -186,6 +187,13 @@ SIGNATURES = {
     "rt_scene_refit": (I, [P, P, P]),
     "rt_refit_aabbs_host": (I, [SZ, P, P, P]),
     "rt_triangles_from_mesh_device": (I, [I, P, SZ, P, P, SZ, P, P]),
+    "rt_scene_rebuild_device": (I, [P, P, P, P, P, P]),
+    "rt_scene_rebuild": (I, [P, P, P, P, P]),
+    "rt_scene_rebuild_path": (I, [P]),
+    "rt_scene_rebuild_counts": (I, [P, P]),
+    "rt_build_bvh_triangles": (I, [SZ, P, P, P]),
+    "rt_debug_box_weight_host": (I, [P, P, I, I, P]),
+    "rt_debug_box_weight_batch": (I, [I, P, P, I, I, P]),
     "rt_render_opts_default": (None, [P]),
     "rt_shard_rows": (I, [I, I, I, I]),
     "rt_render_device": (I, [P, P, P, P, P, P, P]),

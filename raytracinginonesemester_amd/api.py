@@ -260,6 +260,60 @@ class DeviceScene:
             check(lib().rt_scene_refit(self._handle(), ptr(t), C.byref(ms) if timing else None))
         return ms.value if timing else None
 
+    def rebuild(self, triangles, stream: Optional[int] = None, timing: bool = False, tree: bool = False):
+        """New triangles and a new tree under the scene (rt_scene_rebuild / rt_scene_rebuild_device):
+        ``triangles`` as ``refit`` takes them (a numpy (P, 18) array, or a tensor on the scene's
+        device, which takes the device entry on ``stream``).  The tree is the reference's LBVH over
+        them (build_bvh_triangles), built on the device; every packed array and the refit plan are
+        what a refittable scene created from (that tree, triangles) holds, byte for byte, packed on
+        the device too where the tree and the knobs allow (``rebuild_path``).  An error
+        (a vertex that is not finite, quantised records) leaves the scene as it was.
+        ``tree=True`` also returns (nodes (2P-1, 4) uint32, aabbs (2P-1, 6) float32), as numpy
+        arrays or, for a tensor, device tensors (nodes as int32 bit patterns).  The return value is
+        None, ms (``timing``), (nodes, aabbs) (``tree``) or (ms, nodes, aabbs) (both).  Only for
+        scenes made with ``refittable=True``."""
+        ms = C.c_float(0.0)
+        P = self.num_triangles
+        NN = 2 * P - 1
+        nodes = aabbs = None
+        if type(triangles).__module__.split(".")[0] == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if triangles.device != dev or triangles.dtype != torch.float32 or triangles.numel() != 18 * P:
+                raise ValueError(f"rebuild: expects a ({P}, 18) float32 tensor on {dev}")
+            t = triangles.contiguous()
+            if tree:
+                nodes = torch.empty((NN, 4), dtype=torch.int32, device=dev)
+                aabbs = torch.empty((NN, 6), dtype=torch.float32, device=dev)
+            check(lib().rt_scene_rebuild_device(self._handle(), t.data_ptr(), _stream_of(stream, dev),
+                                                nodes.data_ptr() if tree else None, aabbs.data_ptr() if tree else None,
+                                                C.byref(ms) if timing else None))
+        else:
+            t = _c(triangles, np.float32)
+            if t.size != 18 * P:
+                raise ValueError(f"rebuild: expects a ({P}, 18) array of triangles")
+            if tree:
+                nodes, aabbs = np.zeros((NN, 4), np.uint32), np.zeros((NN, 6), np.float32)
+            check(lib().rt_scene_rebuild(self._handle(), ptr(t), ptr(nodes), ptr(aabbs), C.byref(ms) if timing else None))
+        if tree:
+            return (ms.value, nodes, aabbs) if timing else (nodes, aabbs)
+        return ms.value if timing else None
+
+    @property
+    def rebuild_path(self) -> int:
+        """RT_REBUILD_* of the latest ``rebuild`` (rt_scene_rebuild_path): RT_REBUILD_DEVICE when the
+        records were packed on the device too, RT_REBUILD_HOST when the host packed them from the
+        device-built tree, RT_REBUILD_NONE before any rebuild."""
+        return int(lib().rt_scene_rebuild_path(self._handle()))
+
+    @property
+    def rebuild_counts(self) -> tuple:
+        """(kernel launches of the latest rebuild's pack on the device, its host read-backs)."""
+        c = np.zeros(2, np.int64)
+        check(lib().rt_scene_rebuild_counts(self._handle(), ptr(c)))
+        return int(c[0]), int(c[1])
+
     def digest(self) -> tuple:
         """(info (21,) int64, digests (22,) uint64) of the resident arrays, read back from the
         device and hashed (rt_debug_scene_digest): rt_debug_scene_pack's words."""
@@ -1700,6 +1754,20 @@ def build_bvh(positions, indices):
     nodes = np.zeros((2 * P - 1, 4), np.uint32)
     aabbs = np.zeros((2 * P - 1, 6), np.float32)
     check(lib().rt_build_bvh(ptr(pos), pos.size // 3, ptr(idx), P, ptr(nodes), ptr(aabbs)))
+    return nodes, aabbs
+
+
+def build_bvh_triangles(triangles):
+    """CPU LBVH over a (P, 18) triangle array (rt_build_bvh_triangles): build_bvh over the 3P
+    vertices v0, v1, v2 with indices 0..3P-1, the tree DeviceScene.rebuild gives a scene.
+    (nodes (2P-1,4), aabbs (2P-1,6)); internal nodes first, leaves from P-1 on."""
+    tr = _c(triangles, np.float32)
+    P = tr.size // 18
+    if P == 0:
+        check(lib().rt_build_bvh_triangles(0, ptr(np.zeros(18, np.float32)), None, None))
+    nodes = np.zeros((2 * P - 1, 4), np.uint32)
+    aabbs = np.zeros((2 * P - 1, 6), np.float32)
+    check(lib().rt_build_bvh_triangles(P, ptr(tr), ptr(nodes), ptr(aabbs)))
     return nodes, aabbs
 
 

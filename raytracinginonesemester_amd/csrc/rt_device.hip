@@ -37,6 +37,7 @@
 //   rt_query.hpp       batched ray queries on a resident scene (rt_trace_rays*, rt_shade_rays*)
 //   rt_path.hpp        path stages for caller hits (rt_path_*): step, begin, compaction, finish
 //   rt_refit.hpp       refit of a resident scene for deforming geometry (rt_scene_refit*), mesh -> triangles
+//   rt_rebuild.hpp     rebuild of a resident scene (rt_scene_rebuild*): the record weight on the device
 //   rt_scan.hpp        the compaction's scan of tile counts (through rt_path.hpp; also used by rt_frame.hip)
 // Separate translation units: rt_scene_pack.cpp (the host half of rt_scene_create: checks, ids,
 // stack bounds, every packed array), rt_records.cpp (host record builders), rt_hw1.hip (the HW1
@@ -196,6 +197,7 @@ struct RenderParams {
 #include "rt_query.hpp"
 #include "rt_path.hpp"
 #include "rt_refit.hpp"
+#include "rt_rebuild.hpp"
 
 // The render kernel's work: list q's entries, its heavy lists' first (classes in order,
 // heaviest first; each capped at heavy_cap), then its survivors (the cut pass's list, or the
@@ -685,6 +687,8 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     DevBuf rf_order, rf_levels, rf_frec, rf_cut, rf_flag;
     uint32_t rf_n_int = 0, rf_n_leaf = 0, rf_nrec = 0, rf_ncut = 0, rf_ncut2 = 0;
     std::vector<uint32_t> rf_level_off;  // host copy: the launches per level
+    int rebuild_path = RT_REBUILD_NONE;  // RT_REBUILD_* of the latest rt_scene_rebuild[_device] (rt_scene_rebuild_path)
+    int64_t rebuild_launches = 0, rebuild_readbacks = 0;  // ... and its pack's kernel launches and host read-backs
     int binary_stack = 0, wide_stack = 0;  // DFS stack bounds of the records (rt_debug_scene_digest)
     DevBuf work;  // kSets counter sets, then kSets x (live lists | cut survivor lists | heavy lists)
     int64_t last_tiles_total = 0;
@@ -867,6 +871,19 @@ int upload_plan(rt_scene* s, const rt::RefitPlan& plan) {
     return upload_words(s->rf_flag, {});
 }
 
+// The packed facts and arrays into s (rt_scene_create; rt_scene_rebuild's fresh buffers).
+int upload_pack(rt_scene* s, const rt::PackedScene& pk) {
+    static_cast<rt::SceneMeta&>(*s) = pk.meta;
+    s->binary_stack = pk.binary_stack;
+    s->wide_stack = pk.wide_stack;
+    size_t i = 0;
+    for (const rt::PackedArray& a : pk.arrays()) {
+        DevBuf& b = (*s).*kSceneBufs[i++].buf;
+        if (int rc = a.bytes ? b.upload(a.data, a.bytes) : RT_OK; rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
 int scene_create(int device, size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
                  const int32_t* objids, const rt_material* mats, int nmat, const rt_light* lights, int nlights,
                  bool refittable, rt_scene** out) {
@@ -883,17 +900,10 @@ int scene_create(int device, size_t P, const rt_bvh_node* nodes, const rt_aabb* 
     DeviceGuard g(device);
     std::unique_ptr<rt_scene> s(new (std::nothrow) rt_scene());
     if (!s) return set_error(RT_ERR_NOMEM, "out of memory");
-    static_cast<rt::SceneMeta&>(*s) = pk.meta;
     s->device = device;
+    if ((rc = upload_pack(s.get(), pk)) != RT_OK) return rc;
     s->nmat = nmat;
     s->nlights = nlights;
-    s->binary_stack = pk.binary_stack;
-    s->wide_stack = pk.wide_stack;
-    size_t i = 0;
-    for (const rt::PackedArray& a : pk.arrays()) {
-        DevBuf& b = (*s).*kSceneBufs[i++].buf;
-        if (a.bytes && (rc = b.upload(a.data, a.bytes)) != RT_OK) return rc;
-    }
     if (objids && (rc = s->objids.upload(objids, P * sizeof(int32_t))) != RT_OK) return rc;
     if (nmat > 0 && (rc = s->mats.upload(mats, size_t(nmat) * sizeof(rt_material))) != RT_OK) return rc;
     if (nlights > 0 && (rc = s->lights.upload(lights, size_t(nlights) * sizeof(rt_light))) != RT_OK) return rc;
@@ -1072,6 +1082,378 @@ extern "C" int rt_scene_refit(rt_scene* s, const rt_triangle* tris, float* ms) {
     DevBuf d;
     if (int rc = d.upload(tris, s->P * sizeof(rt_triangle)); rc != RT_OK) return rc;
     return rt_scene_refit_device(s, static_cast<const rt_triangle*>(d.p), nullptr, ms);
+}
+
+// ---- rebuild (rt_rebuild.hpp) -----------------------------------------------------
+namespace {
+void swap_bufs(DevBuf& a, DevBuf& b) {
+    std::swap(a.p, b.p);
+    std::swap(a.n, b.n);
+}
+
+int upload_words_of(DevBuf& b, const uint32_t* dev_words, size_t n, hipStream_t st) {  // (upload_words' rule: never empty)
+    if (n == 0) return upload_words(b, {});
+    if (int rc = b.alloc(n * sizeof(uint32_t)); rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(b.p, dev_words, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    return RT_OK;
+}
+
+// rt::pack_scene with a plan on the device (rt_rebuild.hpp), from the tree on the device into the
+// scratch scene t: every array, fact and plan buffer of rt_scene_create_refittable.  *done = false
+// (nothing of t is to be used) when the tree or the knobs are not what the device path handles: the
+// caller then takes the host path.  P >= 2.
+int path_scan_launches(size_t n) { return n <= PATH_TILE ? 1 : 2 + path_scan_launches(path_tiles(n)); }
+
+int rebuild_pack_device(rt_scene* t, size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                        hipStream_t st, bool* done) {
+    *done = false;
+    const size_t n = P - 1;
+    if (P < 2 || P >= (size_t(1) << 25)) return RT_OK;
+    if (int(rt::tuning(RT_TUNE_RECORD_GREEDY, 2.0) + 0.5) != 2 || int(rt::tuning(RT_TUNE_WIDE4_GREEDY, 1.0) + 0.5) != 1 ||
+        rt::tuning(RT_TUNE_QUANT_RECORDS, 0.0) != 0.0)
+        return RT_OK;
+    int rc;
+    const unsigned nb = refit_grid(n);
+    // scratch: 7 words per internal node + the 4-ary entries, the level counts and their scan, the
+    // records' node, id, count and bound per internal node (a record expands one), the cuts
+    const size_t cnt_words = size_t(REBUILD_LEVEL_BINS) * nb;
+    DevBuf w_node, w_cnt, w_rec, w_cut, w_facts;
+    if ((rc = w_node.alloc((6 + 4) * n * 4)) != RT_OK) return rc;
+    if ((rc = w_cnt.alloc((cnt_words + path_scan_words(cnt_words) + 1) * 4)) != RT_OK) return rc;
+    if ((rc = w_rec.alloc((4 * n + path_scan_words(n) + 2 + 33 * n) * 4)) != RT_OK) return rc;
+    if ((rc = w_cut.alloc((6 * 64 + 6 * 64 * 64) * 4 + (64 + 64 * 64 + 1) * 4)) != RT_OK) return rc;
+    if ((rc = w_facts.alloc(128 * 4)) != RT_OK) return rc;
+    uint32_t* wn = static_cast<uint32_t*>(w_node.p);
+    RebuildView v;
+    v.nodes = nodes;
+    v.aabbs = reinterpret_cast<const float*>(aabbs);
+    v.tris = reinterpret_cast<const float*>(tris);
+    v.P = uint32_t(P);
+    v.ht = wn, v.nleaf = wn + n, v.S = wn + 2 * n, v.SW = wn + 3 * n, v.wk = wn + 4 * n, v.went = wn + 6 * n;
+    uint32_t* facts = static_cast<uint32_t*>(w_facts.p);
+    v.flag = facts + 100;
+    HIP_TRY(hipMemsetAsync(facts, 0, 128 * 4, st));
+    // per-node facts bottom-up: one launch per height
+    hipLaunchKernelGGL(rebuild_wide_entries_kernel, dim3(nb), dim3(BLOCK), 0, st, v);
+    HIP_TRY(hipGetLastError());
+    ++t->rebuild_launches;
+    const uint32_t hmax = uint32_t(std::min<size_t>(n, REBUILD_MAX_HEIGHT));
+    for (uint32_t h = 1; h <= hmax; ++h) {
+        hipLaunchKernelGGL(rebuild_level_kernel, dim3(nb), dim3(BLOCK), 0, st, v, h);
+        HIP_TRY(hipGetLastError());
+        ++t->rebuild_launches;
+    }
+    // the plan's order and level offsets
+    uint32_t* cnt = static_cast<uint32_t*>(w_cnt.p);
+    if ((rc = t->rf_order.alloc(n * 4)) != RT_OK) return rc;
+    hipLaunchKernelGGL(rebuild_level_count_kernel, dim3(nb), dim3(BLOCK), 0, st, v, cnt, nb);
+    HIP_TRY(hipGetLastError());
+    ++t->rebuild_launches;
+    t->rebuild_launches += path_scan_launches(cnt_words) - 1;
+    path_scan(cnt, cnt_words, cnt + cnt_words, cnt + cnt_words + path_scan_words(cnt_words), st);
+    HIP_TRY(hipGetLastError());
+    ++t->rebuild_launches;
+    hipLaunchKernelGGL(rebuild_order_kernel, dim3(nb), dim3(BLOCK), 0, st, v, cnt, nb, static_cast<uint32_t*>(t->rf_order.p),
+                       facts);
+    HIP_TRY(hipGetLastError());
+    ++t->rebuild_launches;
+    uint32_t hf[8 + REBUILD_MAX_HEIGHT + 1];
+    HIP_TRY(hipMemcpyAsync(hf, facts, sizeof(hf), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ++t->rebuild_readbacks;
+    const uint32_t top = hf[0];
+    const int sb = int(std::max(1u, hf[1])), sw = int(std::max(1u, hf[2]));
+    // a root without a height (a tree higher than the bound), boxes that are not nested, a deep
+    // tree or a 4-ary stack past the cap: the host path
+    if (top == 0 || top > uint32_t(REBUILD_MAX_HEIGHT) || hf[8] != 0 || hf[3] != 0 || sb > rt::STACK_CAP || sw > rt::STACK_CAP)
+        return RT_OK;
+    std::vector<uint32_t> level_off(hf + 8, hf + 8 + top + 1);
+    if (level_off[top] != n) return RT_OK;
+    // the records by node
+    rt::SceneMeta& m = *t;
+    m = rt::SceneMeta();
+    m.P = P;
+    m.root_ref = 0;
+    m.wide = true;
+    m.lane_stack = sb <= rt::LANE_LDS_CAP;
+    m.lane_wide = m.lane_stack && sw <= rt::LANE_LDS_CAP;
+    m.deep = false;
+    t->binary_stack = sb, t->wide_stack = sw;
+    if ((rc = t->inode.alloc(16 * n * 4)) != RT_OK || (rc = t->ibox.alloc((8 * n + 8) * 4)) != RT_OK ||
+        (rc = t->wnode.alloc(32 * n * 4)) != RT_OK || (rc = t->leaf.alloc(16 * P * 4)) != RT_OK ||
+        (rc = t->tnorm.alloc(12 * P * 4)) != RT_OK)
+        return rc;
+    hipLaunchKernelGGL(rebuild_leaf_kernel, dim3(refit_grid(P)), dim3(BLOCK), 0, st, v, static_cast<float4*>(t->leaf.p));
+    HIP_TRY(hipGetLastError());
+    ++t->rebuild_launches;
+    hipLaunchKernelGGL(rebuild_inode_kernel, dim3(nb), dim3(BLOCK), 0, st, v, static_cast<float*>(t->inode.p),
+                       static_cast<float*>(t->ibox.p), static_cast<float*>(t->wnode.p));
+    HIP_TRY(hipGetLastError());
+    ++t->rebuild_launches;
+    {
+        RefitView rv;
+        std::memset(&rv, 0, sizeof(rv));
+        rv.tnorm = static_cast<float4*>(t->tnorm.p);
+        rv.P = uint32_t(P);
+        hipLaunchKernelGGL(refit_triangles_kernel, dim3(refit_grid(P)), dim3(BLOCK), 0, st, rv, v.tris);
+        HIP_TRY(hipGetLastError());
+        ++t->rebuild_launches;
+    }
+    // the frustum records: the largest arity whose DFS bound fits the cap
+    uint32_t* recnode = static_cast<uint32_t*>(w_rec.p);
+    uint32_t *fid = recnode + n, *rcnt = recnode + 2 * n, *SF = recnode + 3 * n, *rscan = recnode + 4 * n;
+    uint32_t* rtotal = rscan + path_scan_words(n);
+    uint32_t *rk = rtotal + 2, *ents = rk + n;  // a record's entries (32 words) and their number
+    int fr_dmax = int(std::clamp(rt::tuning(RT_TUNE_FRUSTUM_ARITY, 5.0), 2.0, 5.0));
+#ifdef RT_NO_F16
+    fr_dmax = 2;
+#endif
+    const int cap = int(std::clamp(rt::tuning(RT_TUNE_FRUSTUM_STACK_CAP, double(rt::FRUSTUM_STACK)), 1.0, 1e6));
+    size_t nrec = 0;
+    for (int D = fr_dmax; D >= 3 && m.f_log2 == 2; --D) {
+        const int A = 1 << D;
+        HIP_TRY(hipMemsetAsync(recnode, 0, 4, st));  // record 0: the root
+        std::vector<uint32_t> lv{0u, 1u};            // record levels: [lv[k], lv[k + 1])
+        while (lv.back() > lv[lv.size() - 2]) {
+            const uint32_t lo = lv[lv.size() - 2], hi = lv.back();
+            if (lv.size() > size_t(REBUILD_MAX_HEIGHT) + 2) return RT_OK;  // (a level descends a tree level at least)
+            const unsigned g = unsigned((hi - lo + 63) / 64);
+            hipLaunchKernelGGL(rebuild_frec_count_kernel, dim3(g), dim3(64), 0, st, v, recnode, lo, hi, A, rcnt, ents, rk);
+            HIP_TRY(hipGetLastError());
+            ++t->rebuild_launches;
+            t->rebuild_launches += path_scan_launches(hi - lo) - 1;
+            path_scan(rcnt + lo, hi - lo, rscan, rtotal, st);
+            HIP_TRY(hipGetLastError());
+            ++t->rebuild_launches;
+            hipLaunchKernelGGL(rebuild_frec_number_kernel, dim3(refit_grid(hi - lo)), dim3(BLOCK), 0, st, v, recnode, fid, lo, hi,
+                               rcnt, uint32_t(n), ents, rk);
+            HIP_TRY(hipGetLastError());
+            ++t->rebuild_launches;
+            uint32_t total = 0;
+            HIP_TRY(hipMemcpyAsync(&total, rtotal, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            ++t->rebuild_readbacks;
+            if (size_t(hi) + total > n) return RT_OK;  // (cannot be: a record expands one internal node)
+            lv.push_back(hi + total);
+        }
+        nrec = lv.back();
+        for (size_t k = lv.size() - 1; k-- > 0;) {
+            if (lv[k + 1] == lv[k]) continue;
+            hipLaunchKernelGGL(rebuild_frec_bound_kernel, dim3(refit_grid(lv[k + 1] - lv[k])), dim3(BLOCK), 0, st, v, fid, lv[k],
+                               lv[k + 1], SF, ents, rk);
+            HIP_TRY(hipGetLastError());
+            ++t->rebuild_launches;
+        }
+        uint32_t sf0 = 0;
+        HIP_TRY(hipMemcpyAsync(&sf0, SF, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ++t->rebuild_readbacks;
+        if (sf0 > uint32_t(cap)) continue;
+        if ((rc = t->fnode.alloc(size_t(8 * A) * nrec * 4)) != RT_OK) return rc;
+        HIP_TRY(hipMemsetAsync(t->fnode.p, 0, t->fnode.n, st));
+        hipLaunchKernelGGL(rebuild_frec_write_kernel, dim3(refit_grid(nrec << D)), dim3(BLOCK), 0, st, v, fid, uint32_t(nrec), D,
+                           static_cast<float*>(t->fnode.p), ents, rk);
+        HIP_TRY(hipGetLastError());
+        ++t->rebuild_launches;
+        m.f_log2 = D;
+        m.f_bound = int(sf0);
+    }
+    // the cuts
+    const int kcut = int(std::clamp(rt::tuning(RT_TUNE_CULL_BOXES, 64.0), 0.0, 64.0));
+    const int sub = int(std::clamp(rt::tuning(RT_TUNE_CUT_SUB, 16.0), 0.0, 64.0));
+    int sl = 0;
+    while ((2 << sl) <= sub) ++sl;
+    const int S = sub < 2 ? 0 : 1 << sl;
+    float* cutb = static_cast<float*>(w_cut.p);
+    float* cut2b = cutb + 6 * 64;
+    uint32_t* crefs = reinterpret_cast<uint32_t*>(cut2b + 6 * 64 * 64);
+    uint32_t* ncut_dev = crefs + 64 + 64 * 64;
+    uint32_t ncut = 0;
+    if (kcut > 1) {
+        hipLaunchKernelGGL(rebuild_cut_kernel, dim3(1), dim3(64), 0, st, v, kcut, S, cutb, cut2b, crefs, ncut_dev);
+        HIP_TRY(hipGetLastError());
+        ++t->rebuild_launches;
+        HIP_TRY(hipMemcpyAsync(&ncut, ncut_dev, 4, hipMemcpyDeviceToHost, st));
+    }
+    float rootb[8];
+    HIP_TRY(hipMemcpyAsync(rootb, static_cast<const char*>(t->ibox.p) + t->ibox.n - sizeof(rootb), sizeof(rootb),
+                           hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ++t->rebuild_readbacks;
+    if (ncut > 64) return set_error(RT_ERR_INTERNAL, "rebuild: cut size");
+    if (ncut > 0) {
+        if ((rc = t->cut.alloc(size_t(6) * ncut * 4)) != RT_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(t->cut.p, cutb, t->cut.n, hipMemcpyDeviceToDevice, st));
+        m.ncut = int(ncut);
+        if (S >= 2) {
+            if ((rc = t->cut2.alloc(size_t(6) * S * ncut * 4)) != RT_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(t->cut2.p, cut2b, t->cut2.n, hipMemcpyDeviceToDevice, st));
+            m.cut_sub_log2 = sl;
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        m.root_box[a] = rootb[2 * a];
+        m.root_box[3 + a] = rootb[2 * a + 1];
+        m.bmax[a] = std::max(0.f, std::max(std::fabs(rootb[2 * a]), std::fabs(rootb[2 * a + 1])));
+        if (!(m.bmax[a] <= FLT_MAX)) m.bmax[a] = INFINITY;
+    }
+    // the plan (upload_plan's buffers and counts)
+    t->refittable = true;
+    t->rf_n_int = uint32_t(n), t->rf_n_leaf = uint32_t(P);
+    t->rf_nrec = t->fnode.p ? uint32_t(nrec) : 0u;
+    t->rf_ncut = t->cut.p ? ncut : 0u;
+    t->rf_ncut2 = t->cut2.p ? ncut * uint32_t(S) : 0u;
+    t->rf_level_off = level_off;
+    if ((rc = upload_words(t->rf_levels, level_off)) != RT_OK) return rc;
+    if ((rc = upload_words_of(t->rf_frec, recnode, t->rf_nrec, st)) != RT_OK) return rc;
+    if ((rc = t->rf_cut.alloc(std::max<size_t>(1, t->rf_ncut + t->rf_ncut2) * 4)) != RT_OK) return rc;
+    HIP_TRY(hipMemsetAsync(t->rf_cut.p, 0, t->rf_cut.n, st));
+    if (t->rf_ncut) HIP_TRY(hipMemcpyAsync(t->rf_cut.p, crefs, size_t(t->rf_ncut) * 4, hipMemcpyDeviceToDevice, st));
+    if (t->rf_ncut2)
+        HIP_TRY(hipMemcpyAsync(static_cast<uint32_t*>(t->rf_cut.p) + t->rf_ncut, crefs + 64, size_t(t->rf_ncut2) * 4,
+                               hipMemcpyDeviceToDevice, st));
+    if ((rc = upload_words(t->rf_flag, {})) != RT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    *done = true;
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_scene_rebuild_device(rt_scene* s, const rt_triangle* tris_dev, void* hip_stream,
+                                       rt_bvh_node* nodes_out_dev, rt_aabb* aabbs_out_dev, float* ms) {
+    if (!s || !tris_dev) return set_error(RT_ERR_ARG, "rt_scene_rebuild_device: null argument");
+    if (!s->refittable) return set_error(RT_ERR_UNSUPPORTED, "rt_scene_rebuild_device: the scene was not created refittable");
+    DeviceGuard g(s->device);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipStreamSynchronize(s->prep));
+    for (hipStream_t r : s->rstream) HIP_TRY(hipStreamSynchronize(r));
+    HIP_TRY(hipStreamSynchronize(st));
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } ev;
+    if (ms) {
+        *ms = 0.f;
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, st));
+    }
+    const size_t P = s->P, NN = 2 * P - 1;
+    // 1: every vertex coordinate finite (the refit's pass and flag word), before anything is built
+    uint32_t* bad = static_cast<uint32_t*>(s->rf_flag.p);
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(refit_check_kernel, dim3(refit_grid(P)), dim3(BLOCK), 0, st, reinterpret_cast<const float*>(tris_dev),
+                       uint32_t(P), bad);
+    HIP_TRY(hipGetLastError());
+    uint32_t hbad = 0;
+    HIP_TRY(hipMemcpyAsync(&hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hbad) return set_error(RT_ERR_ARG, "rt_scene_rebuild_device: a vertex coordinate is not finite");
+    // 2: the tree, on the device, into buffers of its own
+    DevBuf tn, ta;
+    int rc;
+    if ((rc = tn.alloc(NN * sizeof(rt_bvh_node))) != RT_OK || (rc = ta.alloc(NN * sizeof(rt_aabb))) != RT_OK) return rc;
+    if ((rc = rt::build_bvh_triangles_device(tris_dev, P, static_cast<rt_bvh_node*>(tn.p), static_cast<rt_aabb*>(ta.p), st)) != RT_OK)
+        return rc;
+    // 3: the records, into fresh buffers of a scratch scene; nothing of s has been written so far,
+    // and an error from here to the swap leaves it so.  On the device where the tree and the knobs
+    // allow (rebuild_pack_device), else the host path: the tree and the triangles come back,
+    // rt::pack_scene packs them with a plan, and the arrays go up.
+    std::unique_ptr<rt_scene> t(new (std::nothrow) rt_scene());
+    if (!t) return set_error(RT_ERR_NOMEM, "out of memory");
+    bool on_device = false;
+    if ((rc = rebuild_pack_device(t.get(), P, static_cast<const rt_bvh_node*>(tn.p), static_cast<const rt_aabb*>(ta.p), tris_dev,
+                                  st, &on_device)) != RT_OK)
+        return rc;
+    if (!on_device) {
+        t.reset(new (std::nothrow) rt_scene());
+        if (!t) return set_error(RT_ERR_NOMEM, "out of memory");
+        std::vector<rt_bvh_node> nodes(NN);
+        std::vector<rt_aabb> aabbs(NN);
+        std::vector<rt_triangle> tris(P);
+        HIP_TRY(hipMemcpyAsync(nodes.data(), tn.p, tn.n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(aabbs.data(), ta.p, ta.n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(tris.data(), tris_dev, P * sizeof(rt_triangle), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        rt::PackedScene pk;
+        rt::RefitPlan plan;
+        if ((rc = rt::rebuild_pack(P, nodes.data(), aabbs.data(), tris.data(), pk, plan)) != RT_OK) return rc;
+        if ((rc = upload_pack(t.get(), pk)) != RT_OK || (rc = upload_plan(t.get(), plan)) != RT_OK) return rc;
+    }
+    if (ms) HIP_TRY(hipEventRecord(ev.b, st));
+    if (nodes_out_dev) HIP_TRY(hipMemcpyAsync(nodes_out_dev, tn.p, tn.n, hipMemcpyDeviceToDevice, st));
+    if (aabbs_out_dev) HIP_TRY(hipMemcpyAsync(aabbs_out_dev, ta.p, ta.n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, ev.a, ev.b));
+    // 4: the swap (no call that can fail from here on): the packed arrays and the plan; the
+    // caller's tables (object ids, materials, lights) stay
+    t->nmat = s->nmat;
+    t->nlights = s->nlights;
+    static_cast<rt::SceneMeta&>(*s) = *t;
+    for (size_t i = 0; i < rt::PackedScene::kArrays; ++i) swap_bufs((*s).*kSceneBufs[i].buf, (*t).*kSceneBufs[i].buf);
+    for (DevBuf rt_scene::*b : kRefitBufs) swap_bufs((*s).*b, (*t).*b);
+    s->binary_stack = t->binary_stack, s->wide_stack = t->wide_stack;
+    s->rf_n_int = t->rf_n_int, s->rf_n_leaf = t->rf_n_leaf, s->rf_nrec = t->rf_nrec;
+    s->rf_ncut = t->rf_ncut, s->rf_ncut2 = t->rf_ncut2;
+    s->rf_level_off = std::move(t->rf_level_off);
+    s->bytes = 0;
+    for (const SceneBuf& b : kSceneBufs)
+        if (b.counted) s->bytes += ((*s).*b.buf).n;
+    for (DevBuf rt_scene::*b : kRefitBufs) s->bytes += ((*s).*b).n;
+    s->cost_key = 0;  // the per-tile cost history is the old geometry's
+    s->rebuild_path = on_device ? RT_REBUILD_DEVICE : RT_REBUILD_HOST;
+    s->rebuild_launches = on_device ? t->rebuild_launches : 0;
+    s->rebuild_readbacks = on_device ? t->rebuild_readbacks : 3;  // (host path: the tree, the boxes, the triangles)
+    return RT_OK;
+}
+
+extern "C" int rt_scene_rebuild(rt_scene* s, const rt_triangle* tris, rt_bvh_node* nodes_out, rt_aabb* aabbs_out, float* ms) {
+    if (!s || !tris) return set_error(RT_ERR_ARG, "rt_scene_rebuild: null argument");
+    if (!s->refittable) return set_error(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: the scene was not created refittable");
+    DeviceGuard g(s->device);
+    const size_t NN = 2 * s->P - 1;
+    DevBuf d, tn, ta;
+    int rc;
+    if ((rc = d.upload(tris, s->P * sizeof(rt_triangle))) != RT_OK) return rc;
+    if (nodes_out && (rc = tn.alloc(NN * sizeof(rt_bvh_node))) != RT_OK) return rc;
+    if (aabbs_out && (rc = ta.alloc(NN * sizeof(rt_aabb))) != RT_OK) return rc;
+    rc = rt_scene_rebuild_device(s, static_cast<const rt_triangle*>(d.p), nullptr, static_cast<rt_bvh_node*>(tn.p),
+                                 static_cast<rt_aabb*>(ta.p), ms);
+    if (rc != RT_OK) return rc;
+    if (nodes_out) HIP_TRY(hipMemcpy(nodes_out, tn.p, tn.n, hipMemcpyDeviceToHost));
+    if (aabbs_out) HIP_TRY(hipMemcpy(aabbs_out, ta.p, ta.n, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_scene_rebuild_path(const rt_scene* s) { return s ? s->rebuild_path : RT_REBUILD_NONE; }
+
+extern "C" int rt_scene_rebuild_counts(const rt_scene* s, int64_t counts[2]) {
+    if (!s || !counts) return set_error(RT_ERR_ARG, "rt_scene_rebuild_counts: null argument");
+    counts[0] = s->rebuild_launches;
+    counts[1] = s->rebuild_readbacks;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_box_weight_batch(int device, const float* boxes, const uint32_t* leaves, int rule, int n, double* out) {
+    if (n < 0 || (n > 0 && (!boxes || !leaves || !out)) || (rule != 1 && rule != 2))
+        return set_error(RT_ERR_ARG, "rt_debug_box_weight_batch: bad args (rules 1 and 2)");
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(device);
+    DevBuf db, dl, dout;
+    if ((rc = db.upload(boxes, size_t(n) * 6 * sizeof(float))) != RT_OK) return rc;
+    if ((rc = dl.upload(leaves, size_t(n) * sizeof(uint32_t))) != RT_OK) return rc;
+    if ((rc = dout.alloc(size_t(n) * sizeof(double))) != RT_OK) return rc;
+    hipLaunchKernelGGL(box_weight_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr,
+                       static_cast<const float*>(db.p), static_cast<const uint32_t*>(dl.p), rule, n, static_cast<double*>(dout.p));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, size_t(n) * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 extern "C" int rt_triangles_from_mesh_device(int device, const rt_vec3* positions_dev, size_t num_vertices,

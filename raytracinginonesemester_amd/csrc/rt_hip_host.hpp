@@ -73,5 +73,9 @@ void scene_frame_events(const rt_scene* s, hipEvent_t* first, hipEvent_t* last, 
 // frame slot) lets a scene's frame pre-passes skip the wait for the work queued before the
 // frame on its stream, so they overlap the previous frame's render kernel (rt_device.hip).
 void scene_set_caller_ordered(rt_scene* s, bool on);
+// rt_build_bvh_device's tree over a triangle array (rt_lbvh.hip): the build over the 3P vertices
+// v0, v1, v2 of each triangle with indices 0..3P-1, on the current device; synchronises st.
+int build_bvh_triangles_device(const rt_triangle* tris_dev, size_t P, rt_bvh_node* nodes_dev, rt_aabb* aabbs_dev,
+                               hipStream_t st);
 
 }  // namespace rt

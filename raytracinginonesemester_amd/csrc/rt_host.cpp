@@ -856,6 +856,21 @@ extern "C" int rt_build_bvh(const rt_vec3* positions, size_t num_vertices, const
     return build_bvh_from_mesh(positions, num_vertices, indices, num_triangles, nodes, aabbs);
 }
 
+// rt_build_bvh over the 3P vertices v0, v1, v2 of each triangle with indices 0..3P-1: the tree
+// rt_scene_rebuild gives a scene.
+extern "C" int rt_build_bvh_triangles(size_t P, const rt_triangle* tris, rt_bvh_node* nodes, rt_aabb* aabbs) {
+    if (!tris || !nodes || !aabbs) return set_error(RT_ERR_ARG, "rt_build_bvh_triangles: null argument");
+    if (P == 0) return set_error(RT_ERR_ARG, "no triangles");
+    if (P > 0x3FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^30 triangles");
+    std::vector<rt_vec3> pos(3 * P);
+    std::vector<uint32_t> idx(3 * P);
+    for (size_t i = 0; i < P; ++i) {
+        pos[3 * i] = tris[i].v0, pos[3 * i + 1] = tris[i].v1, pos[3 * i + 2] = tris[i].v2;
+        idx[3 * i] = uint32_t(3 * i), idx[3 * i + 1] = uint32_t(3 * i + 1), idx[3 * i + 2] = uint32_t(3 * i + 2);
+    }
+    return build_bvh_from_mesh(pos.data(), pos.size(), idx.data(), P, nodes, aabbs);
+}
+
 // ---------------------------------------------------------------------------------------
 // Host scene
 // ---------------------------------------------------------------------------------------

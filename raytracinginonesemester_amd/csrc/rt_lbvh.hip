@@ -104,36 +104,26 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
 }
 
 // calculateAABBs (bvh.cu:73-88, aabb_of_triangle bvh.h:54-72 with eps = 0) + the scene-box
-// keys.  A triangle with an out-of-range vertex index raises *err (the host build's check).
-__global__ __launch_bounds__(BLOCK) void leaf_boxes_kernel(const rt_vec3* __restrict__ pos, uint32_t nv,
-                                                           const uint32_t* __restrict__ idx, uint32_t P,
-                                                           rt_aabb* __restrict__ boxes, BoundKeys* keys,
-                                                           int* err) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+// keys, for lane i's triangle A, B, C (have: the lane has one).  Every lane of the block calls it.
+__device__ __forceinline__ void leaf_box_and_keys(bool have, const float A[3], const float B[3], const float C[3],
+                                                  uint32_t i, rt_aabb* __restrict__ boxes, BoundKeys* keys) {
     unsigned long long kmin[3] = {~0ull, ~0ull, ~0ull}, kmax[3] = {0ull, 0ull, 0ull};
-    if (i < P) {
-        const uint32_t a = idx[3 * (size_t)i], b = idx[3 * (size_t)i + 1], c = idx[3 * (size_t)i + 2];
-        if (a >= nv || b >= nv || c >= nv) {
-            atomicOr(err, 1);
-        } else {
-            const rt_vec3 va = pos[a], vb = pos[b], vc = pos[c];
-            const float A[3] = {va.x, va.y, va.z}, B[3] = {vb.x, vb.y, vb.z}, C[3] = {vc.x, vc.y, vc.z};
-            Box bx;
+    if (have) {
+        Box bx;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                // box.minCorner -= 0.0f / maxCorner += 0.0f: x - 0 == x and x + 0 == x bit for bit
-                // except -0 + 0 = +0 (round to nearest), which the max side reproduces here.
-                bx.mn[k] = ref_fminf(A[k], ref_fminf(B[k], C[k])) - 0.0f;
-                bx.mx[k] = ref_fmaxf(A[k], ref_fmaxf(B[k], C[k])) + 0.0f;
-            }
-            store_box(boxes, i, bx);
+        for (int k = 0; k < 3; ++k) {
+            // box.minCorner -= 0.0f / maxCorner += 0.0f: x - 0 == x and x + 0 == x bit for bit
+            // except -0 + 0 = +0 (round to nearest), which the max side reproduces here.
+            bx.mn[k] = ref_fminf(A[k], ref_fminf(B[k], C[k])) - 0.0f;
+            bx.mx[k] = ref_fmaxf(A[k], ref_fmaxf(B[k], C[k])) + 0.0f;
+        }
+        store_box(boxes, i, bx);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                kmin[k] = ((unsigned long long)ord(bx.mn[k], 0xFFFFFFFFu) << 32) | (uint32_t)~i;
-                kmax[k] = ((unsigned long long)ord(bx.mx[k], 0u) << 32) | i;
-                if (bx.mn[k] != bx.mn[k]) kmin[k] = ~0ull;
-                if (bx.mx[k] != bx.mx[k]) kmax[k] = 0ull;
-            }
+        for (int k = 0; k < 3; ++k) {
+            kmin[k] = ((unsigned long long)ord(bx.mn[k], 0xFFFFFFFFu) << 32) | (uint32_t)~i;
+            kmax[k] = ((unsigned long long)ord(bx.mx[k], 0u) << 32) | i;
+            if (bx.mn[k] != bx.mn[k]) kmin[k] = ~0ull;
+            if (bx.mx[k] != bx.mx[k]) kmax[k] = 0ull;
         }
     }
     __shared__ unsigned long long red[BLOCK / 64][6];
@@ -154,6 +144,44 @@ __global__ __launch_bounds__(BLOCK) void leaf_boxes_kernel(const rt_vec3* __rest
         if (k < 3) { if (v != ~0ull) atomicMin(&keys->k[k], v); }
         else if (v != 0ull) atomicMax(&keys->k[k], v);
     }
+}
+
+// ... of an indexed mesh.  A triangle with an out-of-range vertex index raises *err (the host
+// build's check).
+__global__ __launch_bounds__(BLOCK) void leaf_boxes_kernel(const rt_vec3* __restrict__ pos, uint32_t nv,
+                                                           const uint32_t* __restrict__ idx, uint32_t P,
+                                                           rt_aabb* __restrict__ boxes, BoundKeys* keys,
+                                                           int* err) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    float A[3] = {0.f, 0.f, 0.f}, B[3] = {0.f, 0.f, 0.f}, C[3] = {0.f, 0.f, 0.f};
+    bool have = false;
+    if (i < P) {
+        const uint32_t a = idx[3 * (size_t)i], b = idx[3 * (size_t)i + 1], c = idx[3 * (size_t)i + 2];
+        if (a >= nv || b >= nv || c >= nv) {
+            atomicOr(err, 1);
+        } else {
+            const rt_vec3 va = pos[a], vb = pos[b], vc = pos[c];
+            A[0] = va.x, A[1] = va.y, A[2] = va.z;
+            B[0] = vb.x, B[1] = vb.y, B[2] = vb.z;
+            C[0] = vc.x, C[1] = vc.y, C[2] = vc.z;
+            have = true;
+        }
+    }
+    leaf_box_and_keys(have, A, B, C, i, boxes, keys);
+}
+
+// ... of a triangle array (rt_triangle: v0, v1, v2, then the normals; 18 floats): the build over
+// the 3P vertices with indices 0..3P-1 (rt_build_bvh_triangles).
+__global__ __launch_bounds__(BLOCK) void leaf_boxes_tris_kernel(const float* __restrict__ tris, uint32_t P,
+                                                                rt_aabb* __restrict__ boxes, BoundKeys* keys) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    float A[3] = {0.f, 0.f, 0.f}, B[3] = {0.f, 0.f, 0.f}, C[3] = {0.f, 0.f, 0.f};
+    if (i < P) {
+        const float* t = tris + 18 * (size_t)i;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) A[k] = t[k], B[k] = t[3 + k], C[k] = t[6 + k];
+    }
+    leaf_box_and_keys(i < P, A, B, C, i, boxes, keys);
 }
 
 // The scene box from the reduction keys: the winning leaf's coordinate (AABB() if none).
@@ -348,21 +376,10 @@ __global__ __launch_bounds__(TOP_BLOCK) void refit_top_kernel(const rt_bvh_node*
 
 unsigned grid_of(size_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
-}  // namespace
-
-extern "C" int rt_build_bvh_device(int device, const rt_vec3* positions_dev, size_t num_vertices,
-                                   const uint32_t* indices_dev, size_t num_triangles, rt_bvh_node* nodes_dev,
-                                   rt_aabb* aabbs_dev, void* hip_stream) {
-    if (!positions_dev || !indices_dev || !nodes_dev || !aabbs_dev)
-        return set_error(RT_ERR_ARG, "rt_build_bvh_device: null argument");
-    const size_t P = num_triangles;
-    if (P == 0) return set_error(RT_ERR_ARG, "no triangles");
-    if (P > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^31-1 triangles");
-    if (num_vertices > 0xFFFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^32-1 vertices");
-    int rc = rt::check_device(device);
-    if (rc != RT_OK) return rc;
-    DeviceGuard g(device);
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+// The build from the leaf boxes on: launch_leaf_boxes(boxes, keys, err) queues the kernel that
+// writes the P unsorted leaf boxes and the scene-box keys on st.  Synchronises st.
+template <class LeafBoxes>
+int build_lbvh(size_t P, rt_bvh_node* nodes_dev, rt_aabb* aabbs_dev, hipStream_t st, LeafBoxes&& launch_leaf_boxes) {
     const uint32_t n = (uint32_t)P;
     // One stream-ordered workspace (pooled by the runtime across builds): unsorted leaf boxes,
     // Morton codes + triangle ids (double-buffered for the sort), 64-bit keys, node ranges,
@@ -398,8 +415,7 @@ extern "C" int rt_build_bvh_device(int device, const rt_vec3* positions_dev, siz
     for (int k = 0; k < 3; ++k) { init.k[k] = ~0ull; init.k[3 + k] = 0ull; }
     HIP_TRY(hipMemcpyAsync(keys, &init, sizeof(init), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(err, 0, 8, st));  // err + top_count
-    hipLaunchKernelGGL(leaf_boxes_kernel, dim3(grid_of(P)), dim3(BLOCK), 0, st, positions_dev,
-                       (uint32_t)num_vertices, indices_dev, n, bx, keys, err);
+    launch_leaf_boxes(bx, keys, err);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(morton_kernel, dim3(grid_of(P)), dim3(BLOCK), 0, st, bx, n, keys, c0, t0);
     HIP_TRY(hipGetLastError());
@@ -422,4 +438,35 @@ extern "C" int rt_build_bvh_device(int device, const rt_vec3* positions_dev, siz
     HIP_TRY(hipStreamSynchronize(st));
     if (herr) return set_error(RT_ERR_ARG, "triangle index out of range");
     return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_build_bvh_device(int device, const rt_vec3* positions_dev, size_t num_vertices,
+                                   const uint32_t* indices_dev, size_t num_triangles, rt_bvh_node* nodes_dev,
+                                   rt_aabb* aabbs_dev, void* hip_stream) {
+    if (!positions_dev || !indices_dev || !nodes_dev || !aabbs_dev)
+        return set_error(RT_ERR_ARG, "rt_build_bvh_device: null argument");
+    const size_t P = num_triangles;
+    if (P == 0) return set_error(RT_ERR_ARG, "no triangles");
+    if (P > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^31-1 triangles");
+    if (num_vertices > 0xFFFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "more than 2^32-1 vertices");
+    int rc = rt::check_device(device);
+    if (rc != RT_OK) return rc;
+    DeviceGuard g(device);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return build_lbvh(P, nodes_dev, aabbs_dev, st, [&](rt_aabb* bx, BoundKeys* keys, int* err) {
+        hipLaunchKernelGGL(leaf_boxes_kernel, dim3(grid_of(P)), dim3(BLOCK), 0, st, positions_dev,
+                           (uint32_t)num_vertices, indices_dev, (uint32_t)P, bx, keys, err);
+    });
+}
+
+// The same tree over a triangle array on the current device (rt_scene_rebuild_device): the build
+// over the 3P vertices v0, v1, v2 of each triangle with indices 0..3P-1.
+int rt::build_bvh_triangles_device(const rt_triangle* tris_dev, size_t P, rt_bvh_node* nodes_dev, rt_aabb* aabbs_dev,
+                                   hipStream_t st) {
+    return build_lbvh(P, nodes_dev, aabbs_dev, st, [&](rt_aabb* bx, BoundKeys* keys, int*) {
+        hipLaunchKernelGGL(leaf_boxes_tris_kernel, dim3(grid_of(P)), dim3(BLOCK), 0, st,
+                           reinterpret_cast<const float*>(tris_dev), (uint32_t)P, bx, keys);
+    });
 }

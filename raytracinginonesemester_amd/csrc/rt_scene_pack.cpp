@@ -518,6 +518,13 @@ int refit_packed(PackedScene& pk, const RefitPlan& plan, const rt_triangle* tris
     return RT_OK;
 }
 
+int rebuild_pack(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris, PackedScene& out,
+                 RefitPlan& plan) {
+    if (!tris) return set_error(RT_ERR_ARG, "rebuild: null triangles");
+    if (!finite_vertices(P, tris)) return set_error(RT_ERR_ARG, "rebuild: a vertex coordinate is not finite");
+    return pack_scene(P, nodes, aabbs, tris, out, &plan);
+}
+
 void scene_info_words(const SceneMeta& m, int binary_stack, int wide_stack, int64_t info[21]) {
     const int64_t facts[12] = {int64_t(m.P), m.root_ref,  m.ncut, m.cut_sub_log2, m.wide,       m.lane_stack,
                                m.lane_wide,  m.deep,      m.f_log2, m.f_bound,    binary_stack, wide_stack};
@@ -563,6 +570,17 @@ extern "C" int rt_debug_frustum_records(size_t P, const rt_bvh_node* nodes, cons
     info[1] = fr.bound;
     info[2] = (int64_t)fr.nrec;
     if (rec && rec_cap >= fr.rec.size() && !fr.rec.empty()) std::memcpy(rec, fr.rec.data(), fr.rec.size() * sizeof(float));
+    return RT_OK;
+}
+
+// rt::box_weight (rt_records.hpp) for the tests, beside the device build's rt_debug_box_weight_batch:
+// boxes n x (min corner, max corner), leaves n.
+extern "C" int rt_debug_box_weight_host(const float* boxes, const uint32_t* leaves, int rule, int n, double* out) {
+    if (n < 0 || (n > 0 && (!boxes || !leaves || !out))) return set_error(RT_ERR_ARG, "rt_debug_box_weight_host: bad args");
+    for (int i = 0; i < n; ++i) {
+        const float* b = boxes + 6 * size_t(i);
+        out[i] = rt::box_weight(rt_aabb{{b[0], b[1], b[2]}, {b[3], b[4], b[5]}}, rule, leaves[i]);
+    }
     return RT_OK;
 }
 

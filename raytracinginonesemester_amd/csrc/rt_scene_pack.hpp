@@ -93,6 +93,11 @@ int check_proper_tree(size_t P, const rt_bvh_node* nodes, std::vector<uint32_t>*
 // root_box and bmax.  RT_ERR_ARG, touching nothing, when a vertex coordinate is not finite.
 int refit_packed(PackedScene& pk, const RefitPlan& plan, const rt_triangle* tris);
 
+// The host half of rt_scene_rebuild's host path: RT_ERR_ARG when a vertex coordinate is not finite,
+// else pack_scene with a plan of (the tree built over tris, tris).
+int rebuild_pack(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris, PackedScene& out,
+                 RefitPlan& plan);
+
 // rt_debug_scene_pack's words: the facts as info[21], and the FNV-1a hash of an array's bytes.
 void scene_info_words(const SceneMeta& m, int binary_stack, int wide_stack, int64_t info[21]);
 uint64_t fnv1a(const void* data, size_t bytes);
