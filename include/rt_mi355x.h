@@ -1021,7 +1021,9 @@ int rt_kernel_times(const rt_scene* s, float* ms_out, int max, int* n_out);
 /* The same for the whole device frame: the root-box cull pass and the tree-cut cull pass (when
  * it runs), timed on the scene's prep stream, plus the render kernel.  (A frame's pre-passes
  * overlap the previous frame's render kernel, so this is the frame's device work, not the
- * span from its first launch to its end.) */
+ * span from its first launch to its end.)  An rt_renderer's frames on the frame streams
+ * (RT_TUNE_FRAME_STREAMS) carry the pre-passes' events on the frames whose render kernel is timed,
+ * so this and rt_prepass_times report over those frames, as rt_kernel_times does. */
 int rt_frame_times(const rt_scene* s, float* ms_out, int max, int* n_out);
 /* The pre-passes alone (root-box cull + tree-cut cull). */
 int rt_prepass_times(const rt_scene* s, float* ms_out, int max, int* n_out);
@@ -1076,12 +1078,14 @@ typedef enum {
                                     pre-passes when its first work queue has handed out the fraction
                                     f of its items (0.5 default; 1: drained, they then fill its
                                     tail); 0: they start when the frame before it has finished.
-                                    Off while RT_TUNE_OVERLAP_FRAMES is on */
+                                    Off while RT_TUNE_OVERLAP_FRAMES is on without RT_TUNE_FRAME_STREAMS */
     RT_TUNE_OVERLAP_FRAMES = 14, /* rt_renderer frames: 1 lets a frame's render kernel start while the previous
-                                    one's tail still runs (two render streams per scene); 0 (default) */
+                                    one's tail still runs (two render streams per scene); 0 (default).
+                                    Frames on the frame streams (RT_TUNE_FRAME_STREAMS) overlap anyway */
     RT_TUNE_KERNEL_TIMING_EVERY = 15, /* rt_renderer frames: the render kernel's start event (kernel times) in one
-                                    frame of this many (4); an event before every kernel held each
-                                    dispatch ~5 us */
+                                    frame of this many (4; 16 on the frame streams, RT_TUNE_FRAME_STREAMS,
+                                    where the pre-passes' events ride on the same frames); an event
+                                    before every kernel held each dispatch ~5 us */
     RT_TUNE_RECORD_GREEDY = 16,  /* frustum records grown by expanding the entry of largest weight: 2
                                     (default) surface area x sqrt(leaves below), 1 surface area;
                                     0: every path to the same depth; at scene creation */
@@ -1112,7 +1116,14 @@ typedef enum {
                                     (each tile's last item); default 2 */
     RT_TUNE_HW1_CHUNK = 24,      /* the HW1 scene's render work items: list entries per item, 16..256, a power of two
                                     (32) */
-    RT_TUNE_COUNT = 25
+    RT_TUNE_FRAME_STREAMS = 25,  /* rt_renderer's single frames of an unsharded image: 1 (default) puts a frame's
+                                    gate wait, cull, cut and render kernel on one of two streams of
+                                    the scene, alternating by frame, so the three launches follow
+                                    each other on one hardware queue with no event between them
+                                    (the pre-passes' events then ride on the timed frames only, and
+                                    the gate has a word per stream); 0 the pre-passes on the scene's
+                                    prep stream and the render kernel on the caller's */
+    RT_TUNE_COUNT = 26
 } rt_tune_id;
 /* Set knob id (NaN restores the default).  RT_ERR_ARG for an unknown id. */
 int rt_tuning_set(int id, double value);

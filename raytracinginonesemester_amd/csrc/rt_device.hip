@@ -661,6 +661,12 @@ using rt::DevBuf;
 using rt::check_device;
 using rt::DeviceGuard;
 
+// The scene's two frame streams (rt_scene::rstream) at the pre-pass stream's high priority (0,
+// the default) or at normal priority (1: the A/B build of DESIGN.md §4.9).
+#ifndef RT_FRAME_STREAMS_NORMAL
+#define RT_FRAME_STREAMS_NORMAL 0
+#endif
+
 struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hpp), then its device state
     int device = 0;
     const char* last_kernel = nullptr;  // the render kernel instantiation of the latest frame
@@ -706,6 +712,12 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     //   prep:   [wait ev1 of frame k-2 (k-1 too if the outputs overlap)] ev0 | cull | cut | pdone
     //   caller: [wait pdone] evm | render kernel | ev1
     // so frame k's pre-passes overlap frame k-1's render kernel (its tail leaves CUs idle).
+    // Frame streams (RT_TUNE_FRAME_STREAMS, rt_renderer's single frames): the whole chain of frame
+    // k sits on rstream[k & 1],
+    //   rstream[k & 1]: [gate wait] cull | cut | render kernel | ev1
+    // so cull -> cut -> render are same-queue successions with no event between them, "frame k
+    // waits for frame k-2" is stream order, and the chain still overlaps frame k-1's render
+    // kernel, which runs on the other stream.  ev0, pdone and evm ride only on the timed frames.
     static constexpr int kRing = 256;
     hipEvent_t ev0[kRing] = {}, evm[kRing] = {}, ev1[kRing] = {}, pdone[kRing] = {};
     // evm is recorded (the render kernel's start timestamp) only for timed frames: a start event
@@ -713,6 +725,10 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     // written, ~5 us between back-to-back kernels (scripts/micro/kernel_gap.hip); the
     // renderer's frames time one in RT_TUNE_KERNEL_TIMING_EVERY
     bool timed[kRing] = {};
+    // ev0 and pdone of the slot were recorded: every frame of the prep-stream schedule; of the
+    // frame streams' the timed frames, and every frame while the caller reads the frame's start
+    // (want_start)
+    bool ptimed[kRing] = {};
     // frames of the slot's render launch: 2 for the frames of a pair (rt::render_pair; frame A's
     // events bracket the pair kernel, frame B's ev1 is recorded after it), else 1
     uint8_t span[kRing] = {};
@@ -722,15 +738,30 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     // its buffer reuse itself on the host (rt_renderer) sets caller_ordered and skips it.
     hipEvent_t evq[kRing] = {};
     bool caller_ordered = false;
+    bool want_start = true;  // the caller reads every frame's ev0 (rt::scene_set_caller_ordered)
     hipStream_t prep = nullptr;
-    // RT_TUNE_OVERLAP_FRAMES (caller-ordered frames only): render kernels alternate over these
-    // two streams, so frame k+1's kernel takes the wave slots frame k's tail leaves
+    // Caller-ordered frames only.  RT_TUNE_FRAME_STREAMS: frame k's gate wait, pre-passes and
+    // render kernel on rstream[k & 1].  RT_TUNE_OVERLAP_FRAMES without it: the render kernels
+    // alone alternate over the two, the pre-passes stay on prep.  Either way frame k+1's kernel
+    // takes the wave slots frame k's tail leaves.  Both are created at prep's priority, one after
+    // the other (create_sync): HIP spreads the streams of one priority over the hardware queues
+    // in the order of their creation, so the two get a queue each.
     hipStream_t rstream[2] = {};
+    // the previous frame took the frame streams: a frame in the other schedule than the one
+    // before it first waits, on the host, for everything the scene has queued
+    bool last_fs = false;
+    // the previous frame queued a memset ahead of its cull: the next one waits for it (ev1)
+    bool serialise_next = false;
     uint64_t launches = 0;
-    // the pre-pass gate's host word (RenderParams::drained) and the frame whose render kernel
-    // last stored into it (~0: none)
+    // The pre-pass gate's host words (RenderParams::drained): kDrainStride apart, word 0 for the
+    // frames of the prep-stream schedule and the even frames of the frame streams, word 1 for
+    // their odd frames.  A word takes plain stores, so it has one writer kernel at a time: the
+    // kernels of one stream.  drain_frame: the frame whose render kernel last armed a gate (~0:
+    // none), drain_word: the word it stores into.
+    static constexpr int kDrainStride = 16;
     uint32_t* drain = nullptr;
     uint64_t drain_frame = ~0ull;
+    int drain_word = 0;
     uint64_t est_next = 0;  // the oldest frame not yet seen finished (heavy-threshold estimate)
     size_t bytes = 0;
     // Work buffers rotate over kSets per frame (frame k: set k % 6; its cull pass zeroes the
@@ -768,12 +799,13 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
         int lo = 0, hi = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
         HIP_TRY(hipStreamCreateWithPriority(&prep, hipStreamNonBlocking, hi));
-        for (hipStream_t& r : rstream) HIP_TRY(hipStreamCreateWithFlags(&r, hipStreamNonBlocking));
+        for (hipStream_t& r : rstream)
+            HIP_TRY(hipStreamCreateWithPriority(&r, hipStreamNonBlocking, RT_FRAME_STREAMS_NORMAL ? lo : hi));
         if (int rc = fault.alloc(sizeof(uint32_t)); rc != RT_OK) return rc;
         HIP_TRY(hipMemset(fault.p, 0, sizeof(uint32_t)));
         HIP_TRY(hipDeviceSynchronize());  // (the frames run on non-blocking streams)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&drain), sizeof(uint32_t), hipHostMallocCoherent));
-        *drain = 0;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&drain), 2 * kDrainStride * sizeof(uint32_t), hipHostMallocCoherent));
+        std::fill(drain, drain + 2 * kDrainStride, 0u);
         for (int i = 0; i < kRing; ++i) {
             HIP_TRY(hipEventCreate(&ev0[i]));
             HIP_TRY(hipEventCreate(&evm[i]));
@@ -1776,17 +1808,19 @@ struct PairStage {
     hipStream_t stream = nullptr;
 };
 
-// A frame's pre-passes on the scene's prep stream; ev0 / pdone: their start and end, recorded
-// by the dispatches themselves.
-int launch_prepasses(rt_scene* s, const RenderParams& P, int slot) {
+// A frame's pre-passes on pp (the scene's prep stream, or the frame's own stream); ev0 / pdone:
+// their start and end, recorded by the dispatches themselves when the frame's pre-passes are
+// timed (events: an event in a dispatch holds it, and the one after it, for the timestamp).
+int launch_prepasses(rt_scene* s, const RenderParams& P, int slot, hipStream_t pp, bool events = true) {
     const bool cut = P.cull && P.sc.ncut > 0;
-    hipExtLaunchKernelGGL(tile_cull_kernel, dim3((P.tiles_total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s->prep,
-                          s->ev0[slot], cut ? nullptr : s->pdone[slot], 0, P);
+    hipEvent_t ev0 = events ? s->ev0[slot] : nullptr, pdone = events ? s->pdone[slot] : nullptr;
+    hipExtLaunchKernelGGL(tile_cull_kernel, dim3((P.tiles_total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, pp, ev0,
+                          cut ? nullptr : pdone, 0, P);
     HIP_TRY(hipGetLastError());
     if (cut) {
         // 16 waves per CU; each takes (list, group) pairs grid-stride (c3: about one each)
         const int cut_blocks = 4 * s->cus * (8 / CUT_GROUP);
-        hipExtLaunchKernelGGL(tile_cut_kernel, dim3(cut_blocks), dim3(BLOCK), 0, s->prep, nullptr, s->pdone[slot], 0, P);
+        hipExtLaunchKernelGGL(tile_cut_kernel, dim3(cut_blocks), dim3(BLOCK), 0, pp, nullptr, pdone, 0, P);
         HIP_TRY(hipGetLastError());
     }
     return RT_OK;
@@ -1797,11 +1831,11 @@ int flush_pair_a(rt_scene* s, PairStage& ps) {
     ps.deferred = false;
     const int slot = int(ps.kA % rt_scene::kRing);
     s->span[slot] = 1;
-    if (int rc = launch_prepasses(s, ps.A, slot); rc != RT_OK) return rc;
+    if (int rc = launch_prepasses(s, ps.A, slot, s->prep); rc != RT_OK) return rc;
     HIP_TRY(hipStreamWaitEvent(ps.LA.st, s->pdone[slot], 0));
     launch<RT_KERNEL_WAVE | MODE_WIDE>(ps.A, true, ps.LA);
     HIP_TRY(hipGetLastError());
-    if (ps.A.drained) s->drain_frame = ps.kA;
+    if (ps.A.drained) s->drain_frame = ps.kA, s->drain_word = 0;
     return RT_OK;
 }
 
@@ -2008,6 +2042,7 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
         if (s->cost.n < cost_bytes) {
             if (k > 0) {  // the old buffer may still be written
                 HIP_TRY(hipStreamSynchronize(s->prep));
+                for (hipStream_t r : s->rstream) HIP_TRY(hipStreamSynchronize(r));
                 HIP_TRY(hipEventSynchronize(ev1_of(k - 1)));
             }
             if ((rc = s->cost.alloc(cost_bytes)) != RT_OK) return rc;
@@ -2021,6 +2056,7 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     if (s->work.n < work_bytes) {
         if (k > 0) {  // the old buffers may still be read
             HIP_TRY(hipStreamSynchronize(s->prep));
+            for (hipStream_t r : s->rstream) HIP_TRY(hipStreamSynchronize(r));
             HIP_TRY(hipEventSynchronize(ev1_of(k - 1)));
         }
         if ((rc = s->work.alloc(work_bytes)) != RT_OK) return rc;
@@ -2045,7 +2081,11 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
         if ((rc = flush_pair_a(s, *ps)) != RT_OK) return rc;
     }
     const size_t big_bytes = size_t(std::max(0.0, rt::tuning(RT_TUNE_BIG_SCENE_BYTES, double(kBigSceneBytes))));
-    const bool ovl = s->caller_ordered && rt::tuning(RT_TUNE_OVERLAP_FRAMES, 0.0) > 0.5;
+    // RT_TUNE_FRAME_STREAMS: a caller-ordered single frame of an unsharded image takes the frame
+    // streams (pairs and band shards keep the prep-stream schedule); RT_TUNE_OVERLAP_FRAMES then
+    // adds nothing, the render kernels overlap already
+    const bool fs = s->caller_ordered && !ps && P.band_count == 1 && rt::tuning(RT_TUNE_FRAME_STREAMS, 1.0) > 0.5;
+    const bool ovl = !fs && s->caller_ordered && rt::tuning(RT_TUNE_OVERLAP_FRAMES, 0.0) > 0.5;
     // frame A of a pair: its launch waits for frame B's call (PairStage)
     const bool pair_a = ps && ps->phase == 0 && rt::tuning(RT_TUNE_PAIR_FRAMES, 1.0) > 0.5 && !ovl &&
                         pair_kernel_fits(P, samples, !s->deep && mode == RT_KERNEL_WAVE && P.sc.wide != 0,
@@ -2059,6 +2099,16 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
         if (k > 1) HIP_TRY(hipStreamWaitEvent(st, ev1_of(k - 2), 0));
     }
     s->last_stream = st;
+    // The other schedule than the previous frame's (the knob flipped, or a direct call between a
+    // renderer's frames): no order between the streams of the two holds across the change, and
+    // it is rare, so the host waits for all of them.  So does a frame-stream frame that zeroes
+    // every counter set (after a failed frame): the frame before it runs on the other stream.
+    if (k > 0 && (s->last_fs != fs || (fs && s->counters_dirty))) {
+        HIP_TRY(hipStreamSynchronize(s->prep));
+        for (hipStream_t r : s->rstream) HIP_TRY(hipStreamSynchronize(r));
+        HIP_TRY(hipEventSynchronize(ev1_of(k - 1)));
+    }
+    s->last_fs = fs;
     const int set = int(k % rt_scene::kSets), nset = int((k + 2) % rt_scene::kSets);
     char* base = static_cast<char*>(s->work.p);
     char* lists = base + rt_scene::kSets * kCounterBytes + set * set_bytes;
@@ -2071,22 +2121,33 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     const int slot = int(k % rt_scene::kRing);
     // From the cull launch on, a failure leaves the counter sets unknown (counters_dirty).
     auto frame = [&]() -> int {
-        hipStream_t pp = s->prep;
+        // frame streams: the whole chain on this frame's stream, else the pre-passes on prep
+        hipStream_t pp = fs ? s->rstream[k & 1] : s->prep;
         P.drain_tag = uint32_t(k + 1);
         // set k was last read by frame k-6, set k+2 (zeroed by this cull pass) by frame k-4: a
         // frame waits for frame k-2 (the render kernel before the one its pre-passes overlap).
         // Frame A of a pair, k, waits for frame k-3 (the pair before the one running: frames
         // up to k-3 used the sets the pair reads and zeroes) and covers frame B: the pair's
         // pre-passes are launched together, after B's call has set B up.
-        if (pair_a) {
-            if (k >= 3) HIP_TRY(hipStreamWaitEvent(pp, ev1_of(k - 3), 0));
-        } else if (!pair_b && k >= 2) {
-            HIP_TRY(hipStreamWaitEvent(pp, ev1_of(k - 2), 0));
+        // On the frame streams frame k-2 is the work before this frame on its stream.  (The
+        // pre-passes of frames k and k-1 are then ordered by the gate alone, and not at all
+        // without it: they share no set.  A memset does touch other frames' sets, so the frame
+        // after one waits for that frame.)
+        if (fs) {
+            if (k >= 1 && (overlap || s->serialise_next)) HIP_TRY(hipStreamWaitEvent(pp, ev1_of(k - 1), 0));
+        } else {
+            if (pair_a) {
+                if (k >= 3) HIP_TRY(hipStreamWaitEvent(pp, ev1_of(k - 3), 0));
+            } else if (!pair_b && k >= 2) {
+                HIP_TRY(hipStreamWaitEvent(pp, ev1_of(k - 2), 0));
+            }
+            if (k >= 1 && overlap) HIP_TRY(hipStreamWaitEvent(pp, ev1_of(k - 1), 0));
         }
-        if (k >= 1 && overlap) HIP_TRY(hipStreamWaitEvent(pp, ev1_of(k - 1), 0));
+        s->serialise_next = fs && (s->counters_dirty || cost_reset);
         // the pre-pass gate: frame k-1's render kernel opens it when its first queue drains
         if (k >= 1 && s->drain_frame == k - 1)
-            HIP_TRY(hipStreamWaitValue32(pp, s->drain, uint32_t(k), hipStreamWaitValueGte, 0xFFFFFFFFu));
+            HIP_TRY(hipStreamWaitValue32(pp, s->drain + s->drain_word * rt_scene::kDrainStride, uint32_t(k),
+                                         hipStreamWaitValueGte, 0xFFFFFFFFu));
         if (!s->caller_ordered) {  // stream order for the caller's buffers (see rt_scene::evq)
             HIP_TRY(hipEventRecord(s->evq[slot], st));
             HIP_TRY(hipStreamWaitEvent(pp, s->evq[slot], 0));
@@ -2096,6 +2157,16 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
             s->counters_dirty = false;
         }
         if (cost_reset) HIP_TRY(hipMemsetAsync(s->cost.p, 0, s->cost.n, pp));  // no heavy tiles yet
+        // RT_TUNE_KERNEL_TIMING_EVERY: the caller-ordered (rt_renderer) frames record the render
+        // kernel's start event in one frame of this many (direct calls: every frame); a pair
+        // kernel's start is frame A's (frame B's slot is never timed).  On the frame streams the
+        // pre-passes' events go with it, unless the caller reads every frame's start; there a
+        // timed frame's three events cost ~30 us of its chain (8-17 us each when most frames
+        // carry none), so the default is one frame in 16.
+        const uint64_t every =
+            uint64_t(std::clamp(rt::tuning(RT_TUNE_KERNEL_TIMING_EVERY, fs ? 16.0 : 4.0), 1.0, 256.0));
+        s->timed[slot] = !pair_b && (!s->caller_ordered || k % every == 0 || (pair_a && (k + 1) % every == 0));
+        s->ptimed[slot] = !fs || s->timed[slot] || s->want_start;
         // frame A of a pair: its pre-passes go out with frame B's (pair_b below, or flush_pair_a)
         if (pair_b) {
             // both frames' passes in one cull and one cut launch (the same cut: the pair's tile
@@ -2120,20 +2191,16 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
             }
             HIP_TRY(hipEventRecord(s->pdone[slot_a], pp));
         } else if (!pair_a) {
-            if ((rc = launch_prepasses(s, P, slot)) != RT_OK) return rc;
+            if ((rc = launch_prepasses(s, P, slot, pp, s->ptimed[slot])) != RT_OK) return rc;
         }
+        // Frame streams: the render kernel follows the cut on the frame's stream.
         // RT_TUNE_OVERLAP_FRAMES: the render kernel on one of the scene's two render streams (the
         // caller orders its buffers itself; its stream then waits for the kernel), else on the
         // caller's stream
-        const hipStream_t rs = ovl ? s->rstream[k & 1] : st;
+        const hipStream_t rs = fs ? pp : ovl ? s->rstream[k & 1] : st;
         // (frame A of a pair: frame B's pdone, later on the same prep stream, covers both)
-        if (!pair_a) HIP_TRY(hipStreamWaitEvent(rs, s->pdone[slot], 0));
+        if (!pair_a && !fs) HIP_TRY(hipStreamWaitEvent(rs, s->pdone[slot], 0));
         const bool qr = P.sc.qent != nullptr && P.sc.f_log2 > 2;
-        // RT_TUNE_KERNEL_TIMING_EVERY: the caller-ordered (rt_renderer) frames record the render
-        // kernel's start event in one frame of this many (direct calls: every frame); a pair
-        // kernel's start is frame A's (frame B's slot is never timed)
-        const uint64_t every = uint64_t(std::clamp(rt::tuning(RT_TUNE_KERNEL_TIMING_EVERY, 4.0), 1.0, 256.0));
-        s->timed[slot] = !pair_b && (!s->caller_ordered || k % every == 0 || (pair_a && (k + 1) % every == 0));
         s->span[slot] = pair_a || pair_b ? 2 : 1;
         const Launch L{rs, s->timed[slot] ? s->evm[slot] : nullptr, s->ev1[slot], s->cus, s->bytes > big_bytes, qr,
                        &s->last_kernel};
@@ -2145,9 +2212,11 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
         // The gate word takes plain stores, so it needs one writer kernel at a time: with
         // overlapping frames (ovl: two render streams) a late store of frame k-2's kernel could
         // overwrite frame k-1's tag after frame k had started waiting for it, so ovl runs ungated.
+        // The frame streams have a word each: its writers are the kernels of one stream, in turn.
         const double gate_f = ovl ? 0.0 : rt::tuning(RT_TUNE_PREPASS_GATE, 0.5);
         const bool gate = gate_f > 0.0;
-        P.drained = gate ? s->drain : nullptr;
+        const int word = fs ? int(k & 1) : 0;
+        P.drained = gate ? s->drain + word * rt_scene::kDrainStride : nullptr;
         P.drain_tag = uint32_t(k + 1);
         P.gate_q8 = int(std::clamp(gate_f, 0.0, 1.0) * 256.0 + 0.5);
         if (pair_a) {  // held for frame B's call
@@ -2170,7 +2239,7 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
             launch_pair(A, P, LP);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(s->ev1[slot], rs));
-            if (gate) s->drain_frame = k;
+            if (gate) s->drain_frame = k, s->drain_word = word;
             return RT_OK;
         }
         if (s->deep) launch<MODE_DEEP>(P, samples, L);
@@ -2178,8 +2247,9 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
         else if (P.sc.wide) launch<RT_KERNEL_WAVE | MODE_WIDE>(P, samples, L);
         else launch<RT_KERNEL_WAVE>(P, samples, L);
         HIP_TRY(hipGetLastError());
-        if (ovl) HIP_TRY(hipStreamWaitEvent(st, s->ev1[slot], 0));
-        if (gate) s->drain_frame = k;
+        if (gate) s->drain_frame = k, s->drain_word = word;
+        // the caller's stream follows the frame, as if the kernel had run on it
+        if (ovl || fs) HIP_TRY(hipStreamWaitEvent(st, s->ev1[slot], 0));
         return RT_OK;
     };
     std::copy(std::begin(out_now), std::end(out_now), std::begin(s->prev_out));
@@ -2791,15 +2861,17 @@ extern "C" int rt_path_compact_device(int device, size_t m, const uint8_t* alive
     return RT_OK;
 }
 
-void rt::scene_set_caller_ordered(rt_scene* s, bool on) {
-    if (s) s->caller_ordered = on;
+void rt::scene_set_caller_ordered(rt_scene* s, bool on, bool frame_start) {
+    if (!s) return;
+    s->caller_ordered = on;
+    s->want_start = frame_start;
 }
 
 void rt::scene_frame_events(const rt_scene* s, hipEvent_t* first, hipEvent_t* last, int back) {
     hipEvent_t a = nullptr, b = nullptr;
     if (s && s->launches > uint64_t(back)) {
         const int slot = int((s->launches - 1 - uint64_t(back)) % rt_scene::kRing);
-        a = s->ev0[slot];
+        a = s->ptimed[slot] ? s->ev0[slot] : nullptr;
         b = s->ev1[slot];
     }
     if (first) *first = a;
@@ -2815,11 +2887,12 @@ int event_times(const rt_scene* s, int what, float* ms_out, int max, int* n_out)
     DeviceGuard g(s->device);
     const uint64_t have = std::min<uint64_t>(s->launches, uint64_t(rt_scene::kRing));
     // the most recent frames with a kernel start event (all of them unless the renderer samples,
-    // RT_TUNE_KERNEL_TIMING_EVERY), at most max, oldest first; pre-pass times need no sampling
+    // RT_TUNE_KERNEL_TIMING_EVERY), at most max, oldest first; the pre-passes' events ride on
+    // every frame of the prep-stream schedule and on the timed frames of the frame streams
     std::vector<int> slots;
     for (uint64_t b = 1; b <= have && (int)slots.size() < max; ++b) {
         const int slot = int((s->launches - b) % rt_scene::kRing);
-        if (what == 1 || s->timed[slot]) slots.push_back(slot);
+        if ((what == 0 || s->ptimed[slot]) && (what == 1 || s->timed[slot])) slots.push_back(slot);
     }
     const int n = (int)slots.size();
     for (int k = 0; k < n; ++k) {

@@ -67,12 +67,16 @@ struct DeviceGuard {
 // before its first launch and after its render kernel, both on the frame's stream and owned
 // by the scene (valid for the scene's next 255 frames); nullptr before the first frame.
 // rt_renderer synchronises on these instead of recording events of its own on that stream.
+// first is nullptr for a frame whose start was not recorded (the frame streams' untimed frames of
+// a caller that passed frame_start = false below).
 // back: the frame that many frames before the most recent (1: frame A of a pair just rendered).
 void scene_frame_events(const rt_scene* s, hipEvent_t* first, hipEvent_t* last, int back = 0);
 // A caller that orders the reuse of its output buffers itself (rt_renderer: host waits per
 // frame slot) lets a scene's frame pre-passes skip the wait for the work queued before the
 // frame on its stream, so they overlap the previous frame's render kernel (rt_device.hip).
-void scene_set_caller_ordered(rt_scene* s, bool on);
+// frame_start = false: the caller reads no start event of its frames (scene_frame_events' first),
+// so the frame streams record the pre-passes' events on the timed frames only.
+void scene_set_caller_ordered(rt_scene* s, bool on, bool frame_start = true);
 // rt_build_bvh_device's tree over a triangle array (rt_lbvh.hip): the build over the 3P vertices
 // v0, v1, v2 of each triangle with indices 0..3P-1, on the current device; synchronises st.
 int build_bvh_triangles_device(const rt_triangle* tris_dev, size_t P, rt_bvh_node* nodes_dev, rt_aabb* aabbs_dev,

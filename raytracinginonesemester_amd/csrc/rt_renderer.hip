@@ -897,7 +897,9 @@ int submit_frames(rt_renderer* r, const rt_camera* const* cams, int nf, const rt
             // the renderer waits for buffer reuse on the host: its own frames skip the scene's
             // wait for work queued before them on the compute stream (there is none but its
             // frames).  Only for this call: a borrowed view (rt_renderer_scene) stays stream-ordered.
-            rt::scene_set_caller_ordered(L.scene, true);
+            // (the frame's start event is read below only for rank 0's frames, and not for those
+            // an SDMA copy delivers: their times are the copy's own)
+            rt::scene_set_caller_ordered(L.scene, true, own && !r->dma);
             int q;
             if (nf == 2)
                 q = rt_render_device_pair(L.scene, cams[0], cams[1], &o, f32 ? static_cast<float*>(buf[0]) : nullptr,
