@@ -293,7 +293,10 @@ typedef struct {
     int32_t spp;
     int32_t diffuse_bounce;
     rt_vec3 miss_color;
-    const float* jitter;      /* host, 2*spp floats; NULL = rt_jittered_samples(spp, 42, 1) */
+    const float* jitter;      /* host, 2*spp floats; NULL = rt_jittered_samples(spp, 42, 1).  Any
+                               * table renders exactly.  The tile culling covers tables whose
+                               * every entry is finite with |entry| <= 1 (its one-pixel pad); a
+                               * frame with any other table runs as with RT_FLAG_NO_CULL. */
     /* Image sharding: rows are cut into bands of band_rows; this call renders bands b with
      * b % band_count == band_index, written contiguously (band order) into the output
      * ("strip" layout).  band_count <= 1 renders the whole frame in row-major order. */
@@ -981,6 +984,31 @@ int rt_box_test_host(const float* rays, const float* boxes, const float* tminmax
  * constant 1e-4f. */
 int rt_box_test_batch(int device, const float* rays, const float* boxes, const float* tminmax,
                       const float* bmax, const uint8_t* active, int n, int32_t* out);
+
+/* The group-wide box tests, item by item: the functions the kernels call (one definition each,
+ * host and device builds of the same text), so a fuzz can hold them against the rays themselves.
+ *
+ * The tile test of the cull and cut pre-passes (csrc/rt_prepass.hpp tile_dirs_f,
+ * tile_misses_box_f).  Item i: the pixel rectangle tiles[4i..] = (x0, x1, y0, y1), columns x0..x1
+ * and rows y0..y1 inclusive, of cam's image, and the box boxes[6i..] = (min, max).  out[i] = 1
+ * when the test says every camera ray of the rectangle, for any jitter with |entry| <= 1,
+ * misses the box. */
+int rt_debug_tile_test_host(const rt_camera* cam, const int32_t* tiles, const float* boxes, int n, int32_t* out);
+int rt_debug_tile_test_batch(int device, const rt_camera* cam, const int32_t* tiles, const float* boxes, int n,
+                             int32_t* out);
+
+/* The wave-family entry test of the camera rays' frustum traversal (csrc/rt_traverse.hpp
+ * family_axis, family_entry_passes: what family_dirs and frustum_loop call; float records, not
+ * the quantised ones).  Wave w: 64 rays rays[384w..] (orig, dir; one origin, lane 0's, and
+ * directions as the kernels hold them), active[64w..] bytes (NULL: all live; a wave needs a live
+ * lane), best_t[64w..] the lanes' bestT, bmax[3w..] the scene's per-axis bound of |coordinate|,
+ * and 32 boxes boxes[192w..] (min, max), entry k tested as lane k tests it.  out[32w + k] = 1
+ * when entry k passes with tmax_w = the largest bestT over the live lanes; out_loose[w] = 1 when
+ * the wave has a loose axis (the LOOSE loop form).  The batch form runs one wave per item. */
+int rt_debug_family_test_host(const float* rays, const uint8_t* active, const float* best_t, const float* bmax,
+                              const float* boxes, int n_waves, int32_t* out, int32_t* out_loose);
+int rt_debug_family_test_batch(int device, const float* rays, const uint8_t* active, const float* best_t,
+                               const float* bmax, const float* boxes, int n_waves, int32_t* out, int32_t* out_loose);
 
 /* Host build of the camera rays' frustum records rt_scene_create makes (no device): for a BVH
  * of P triangles (the same arrays as rt_scene_create), the records of arity 2^info[0]

@@ -280,6 +280,10 @@ SIGNATURES = {
     "rt_powf_batch": (I, [I, P, P, I, P]),
     "rt_box_test_host": (I, [P, P, P, I, P, P, P]),
     "rt_box_test_batch": (I, [I, P, P, P, P, P, I, P]),
+    "rt_debug_tile_test_host": (I, [P, P, P, I, P]),
+    "rt_debug_tile_test_batch": (I, [I, P, P, P, I, P]),
+    "rt_debug_family_test_host": (I, [P, P, P, P, P, I, P, P]),
+    "rt_debug_family_test_batch": (I, [I, P, P, P, P, P, I, P, P]),
     "rt_kernel_times": (I, [P, P, I, P]),
     "rt_frame_times": (I, [P, P, I, P]),
     "rt_prepass_times": (I, [P, P, I, P]),

@@ -630,6 +630,61 @@ __global__ __launch_bounds__(BLOCK) void box_test_kernel(const float* __restrict
     }
 }
 
+// The camera words tile_dirs_f reads, from the ABI's camera.
+__host__ __device__ __forceinline__ void tile_test_camera(RenderParams& P, const rt_camera& cam) {
+    P.cam_center = f3{cam.center.x, cam.center.y, cam.center.z};
+    P.cam_p00 = f3{cam.pixel00_loc.x, cam.pixel00_loc.y, cam.pixel00_loc.z};
+    P.cam_du = f3{cam.pixel_delta_u.x, cam.pixel_delta_u.y, cam.pixel_delta_u.z};
+    P.cam_dv = f3{cam.pixel_delta_v.x, cam.pixel_delta_v.y, cam.pixel_delta_v.z};
+}
+
+// rt_debug_tile_test_batch: the device build of the tile test, one lane per item.
+__global__ __launch_bounds__(BLOCK) void tile_test_kernel(RenderParams P, const int32_t* __restrict__ tiles,
+                                                          const float* __restrict__ boxes, int n,
+                                                          int32_t* __restrict__ out) {
+    const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    if (i >= n) return;
+    const int32_t* t = tiles + 4 * (size_t)i;
+    float bx[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) bx[k] = boxes[6 * (size_t)i + k];
+    out[i] = tile_misses_box_f(tile_dirs_f(P, t[0], t[1], t[2], t[3]), bx) ? 1 : 0;
+}
+
+// rt_debug_family_test_batch: one wave per item.  Lane l holds ray l of the wave (family_dirs
+// over the lanes with a nonzero `active` byte, tmax_w as frustum_loop reduces it), then lane k
+// (mod 32) tests entry k with the loop form the wave takes.  Every lane runs the reductions.
+__global__ __launch_bounds__(BLOCK) void family_test_kernel(const float* __restrict__ rays,
+                                                            const uint8_t* __restrict__ active,
+                                                            const float* __restrict__ best_t,
+                                                            const float* __restrict__ bmax,
+                                                            const float* __restrict__ boxes, int n_waves,
+                                                            int32_t* __restrict__ out, int32_t* __restrict__ out_loose) {
+    const int w = (int)(blockIdx.x * (BLOCK / 64) + threadIdx.x / 64);
+    if (w >= n_waves) return;  // (a whole wave)
+    const uint32_t lane = lane_id();
+    const size_t j = (size_t)w * 64 + lane;
+    const float* R = rays + 6 * j;
+    SceneView sc;
+    sc.bmax[0] = bmax[3 * (size_t)w];
+    sc.bmax[1] = bmax[3 * (size_t)w + 1];
+    sc.bmax[2] = bmax[3 * (size_t)w + 2];
+    const RayPre r = make_ray(mk(R[0], R[1], R[2]), mk(R[3], R[4], R[5]), mk(sc.bmax[0], sc.bmax[1], sc.bmax[2]));
+    const bool live = active == nullptr || active[j] != 0;
+    const float o[3] = {__int_as_float(uni(__float_as_int(r.o.x))), __int_as_float(uni(__float_as_int(r.o.y))),
+                        __int_as_float(uni(__float_as_int(r.o.z)))};
+    v2f U[3];
+    const bool loose = family_dirs(sc, r, live, o, U);
+    const float tmax_w = wave_reduce_f<true>(live ? best_t[j] : 0.0f);
+    const float* B = boxes + 6 * ((size_t)w * 32 + (lane & 31u));
+    const v2f bb[3] = {(v2f){B[0], B[3]}, (v2f){B[1], B[4]}, (v2f){B[2], B[5]}};
+    bool pass;
+    if (__builtin_amdgcn_readfirstlane((int)loose) != 0) pass = family_entry_passes<true>(bb, o, U, tmax_w);
+    else pass = family_entry_passes<false>(bb, o, U, tmax_w);
+    if (lane < 32u) out[(size_t)w * 32 + lane] = pass ? 1 : 0;
+    if (lane == 0) out_loose[w] = loose ? 1 : 0;
+}
+
 // Batched ray-triangle queries (KAT path): one lane per ray.
 __global__ __launch_bounds__(BLOCK) void intersect_kernel(f3 v0, f3 e1, f3 e2, f3 o, const float* __restrict__ dirs,
                                                           int n, int hw1, float tmin, float tmax,
@@ -1606,6 +1661,18 @@ int prepare_jitter(rt_scene* s, const rt_render_opts* o) {
     return RT_OK;
 }
 
+// Every entry finite and within the tile tests' one-pixel pad (NaN fails the compare).
+bool jitter_within_pad(const std::vector<float>& tab) {
+    for (const float j : tab)
+        if (!(fabsf(j) <= 1.0f)) return false;
+    return true;
+}
+bool jitter_finite(const std::vector<float>& tab) {
+    for (const float j : tab)
+        if (!std::isfinite(j)) return false;
+    return true;
+}
+
 // The render kernel's persistent grid: the blocks of it one dispatch keeps resident on every CU
 // (the occupancy the kernel was compiled for, LDS permitting), a multiple of 8 (one share per
 // XCD queue), at most one block per tile.  Blocks beyond residency would only find the queues
@@ -1916,7 +1983,13 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
         P.miss_p6[2] = rtp::p6_default_sample(mp.z);
         P.miss_p6[3] = 0;
     }
-    const bool samples = o->kernel != RT_KERNEL_WAVE_PIXELS && o->spp <= BLOCK && (o->spp & (o->spp - 1)) == 0;
+    // A table with a non-finite entry gives that sample's rays a NaN direction.  In the reference
+    // every compare of such a ray is false: every box test passes, every triangle "hits" with t =
+    // NaN, and the ray ends on the last triangle of its own DFS.  The lane kernel is that DFS ray by
+    // ray; the wave kernels' group-wide tests (the family's min / max drop a NaN lane) are not, so
+    // such a frame takes the lane kernel.
+    const int kernel = jitter_finite(s->jitter_host) ? o->kernel : RT_KERNEL_LANE;
+    const bool samples = kernel != RT_KERNEL_WAVE_PIXELS && o->spp <= BLOCK && (o->spp & (o->spp - 1)) == 0;
     // Half waves (32 samples per wave) for the shards of an 8-way split: a shard's kernel is then
     // bound by its longest waves, and halving their rays shortens them (c3 band shards on one
     // GPU, max over the 8: kernel 0.101 -> 0.095 ms, frame 0.122 -> 0.116; at 4 and fewer shards
@@ -1934,7 +2007,7 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     // One light and a tree whose DFS fits the per-lane LDS stacks: the bounce kernels that hold
     // only the paired loop (paired_bounces), fewer live registers than the kernels that also
     // carry the unpaired one.  RT_PAIRED_ONLY=0 turns them off (A/B: the unpaired loop on half waves).
-    P.paired_only = half && o->max_depth > 1 && s->nlights == 1 && !s->deep && o->kernel != RT_KERNEL_LANE &&
+    P.paired_only = half && o->max_depth > 1 && s->nlights == 1 && !s->deep && kernel != RT_KERNEL_LANE &&
                             (P.sc.wide ? s->lane_wide : s->lane_stack)
                         ? 1
                         : 0;
@@ -1953,6 +2026,10 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     P.lane_samples = samples ? 1 : 0;
     P.tile_order = o->tile_order == RT_TILES_AUTO ? RT_TILES_ROWS : o->tile_order;
     P.cull = (o->flags & RT_FLAG_NO_CULL) ? 0 : 1;
+    // The tile tests pad a tile by one pixel (tile_dirs_f): that covers a jitter table whose every
+    // entry is finite with |entry| <= 1, the default table among them.  Any other caller table
+    // (a wide reconstruction filter, a sub-frame shift) renders without the cull: as exact.
+    if (P.cull && !jitter_within_pad(s->jitter_host)) P.cull = 0;
     if (!P.cull) P.sc.ncut = 0;  // the render kernel reads the cut pass's lists only when it ran
     P.miss_pixel = miss_pixel_value(o);
     P.nqueues = P.tile_order == RT_TILES_LINEAR ? 1 : 8;
@@ -1966,7 +2043,7 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     // c3 (frustum traversal, profiles/r04/exp/heavy_frac_ab_c3*.log): 0.05 0.153, 0.06 0.149,
     // 0.08 0.148, 0.10 0.147, 0.12 0.150, 0.18 0.151, 0.25 0.158 ms, off 0.187
     const double heavy_frac = rt::tuning(RT_TUNE_HEAVY_FRAC, 0.10);
-    const int mode = o->kernel == RT_KERNEL_LANE ? RT_KERNEL_LANE : RT_KERNEL_WAVE;
+    const int mode = kernel == RT_KERNEL_LANE ? RT_KERNEL_LANE : RT_KERNEL_WAVE;
     const bool costs = P.cull && P.sc.ncut > 0 && P.nqueues == 8 && heavy_frac > 0.0;
     // RT_TUNE_HEAVY_CAP: entries per (class, list) (speed experiments)
     const int heavy_cap = int(std::clamp(rt::tuning(RT_TUNE_HEAVY_CAP, 512.0), 1.0, 1e9));
@@ -3191,5 +3268,107 @@ extern "C" int rt_box_test_host(const float* rays, const float* boxes, const flo
         out_fast[i] = box_hit(r, b, tminmax[2 * i], tminmax[2 * i + 1]) ? 1 : 0;
         out_exact[i] = box_hit_exact(r, b, (double)tminmax[2 * i], (double)tminmax[2 * i + 1]) ? 1 : 0;
     }
+    return RT_OK;
+}
+
+extern "C" int rt_debug_tile_test_host(const rt_camera* cam, const int32_t* tiles, const float* boxes, int n,
+                                       int32_t* out) {
+    if (!cam || n < 0 || (n > 0 && (!tiles || !boxes || !out))) return set_error(RT_ERR_ARG, "rt_debug_tile_test_host: bad args");
+    RenderParams P;
+    std::memset(&P, 0, sizeof(P));
+    tile_test_camera(P, *cam);
+    for (int i = 0; i < n; ++i) {
+        const int32_t* t = tiles + 4 * size_t(i);
+        out[i] = tile_misses_box_f(tile_dirs_f(P, t[0], t[1], t[2], t[3]), boxes + 6 * size_t(i)) ? 1 : 0;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_debug_tile_test_batch(int device, const rt_camera* cam, const int32_t* tiles, const float* boxes,
+                                        int n, int32_t* out) {
+    if (!cam || n < 0 || (n > 0 && (!tiles || !boxes || !out))) return set_error(RT_ERR_ARG, "rt_debug_tile_test_batch: bad args");
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(device);
+    DevBuf dt, db, dout;
+    if ((rc = dt.upload(tiles, size_t(n) * 4 * sizeof(int32_t))) != RT_OK) return rc;
+    if ((rc = db.upload(boxes, size_t(n) * 6 * sizeof(float))) != RT_OK) return rc;
+    if ((rc = dout.alloc(size_t(n) * sizeof(int32_t))) != RT_OK) return rc;
+    RenderParams P;
+    std::memset(&P, 0, sizeof(P));
+    tile_test_camera(P, *cam);
+    hipLaunchKernelGGL(tile_test_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, P,
+                       static_cast<const int32_t*>(dt.p), static_cast<const float*>(db.p), n, static_cast<int32_t*>(dout.p));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_debug_family_test_host(const float* rays, const uint8_t* active, const float* best_t,
+                                         const float* bmax, const float* boxes, int n_waves, int32_t* out,
+                                         int32_t* out_loose) {
+    if (n_waves < 0 || (n_waves > 0 && (!rays || !best_t || !bmax || !boxes || !out || !out_loose)))
+        return set_error(RT_ERR_ARG, "rt_debug_family_test_host: bad args");
+    for (int w = 0; w < n_waves; ++w) {
+        const float* R = rays + 6 * 64 * size_t(w);
+        const float o[3] = {R[0], R[1], R[2]};  // the shared origin: lane 0's
+        // family_dirs and frustum_loop's tmax_w, the wave reductions as plain loops
+        v2f U[3];
+        bool loose = false;
+        for (int a = 0; a < 3; ++a) {
+            float dl = INFINITY, dh = -INFINITY;
+            for (int l = 0; l < 64; ++l) {
+                if (active && !active[64 * size_t(w) + l]) continue;
+                dl = fminf(dl, R[6 * l + 3 + a]);
+                dh = fmaxf(dh, R[6 * l + 3 + a]);
+            }
+            float u0, u1;
+            const bool lz = family_axis(dl, dh, bmax[3 * size_t(w) + a] + fabsf(o[a]) < 1e30f, u0, u1);
+            loose = loose || lz;
+            U[a] = (v2f){u0, u1};
+        }
+        float tmax_w = 0.0f;
+        for (int l = 0; l < 64; ++l)
+            if (!active || active[64 * size_t(w) + l]) tmax_w = fmaxf(tmax_w, best_t[64 * size_t(w) + l]);
+        out_loose[w] = loose ? 1 : 0;
+        for (int k = 0; k < 32; ++k) {
+            const float* B = boxes + 6 * (32 * size_t(w) + k);
+            const v2f bb[3] = {(v2f){B[0], B[3]}, (v2f){B[1], B[4]}, (v2f){B[2], B[5]}};
+            const bool pass = loose ? family_entry_passes<true>(bb, o, U, tmax_w) : family_entry_passes<false>(bb, o, U, tmax_w);
+            out[32 * size_t(w) + k] = pass ? 1 : 0;
+        }
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_debug_family_test_batch(int device, const float* rays, const uint8_t* active, const float* best_t,
+                                          const float* bmax, const float* boxes, int n_waves, int32_t* out,
+                                          int32_t* out_loose) {
+    if (n_waves < 0 || n_waves > (1 << 24) || (n_waves > 0 && (!rays || !best_t || !bmax || !boxes || !out || !out_loose)))
+        return set_error(RT_ERR_ARG, "rt_debug_family_test_batch: bad args");
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    if (n_waves == 0) return RT_OK;
+    DeviceGuard g(device);
+    const size_t n = size_t(n_waves);
+    DevBuf dr, da, dt, dm, db, dout, dl;
+    if ((rc = dr.upload(rays, n * 64 * 6 * sizeof(float))) != RT_OK) return rc;
+    if (active && (rc = da.upload(active, n * 64)) != RT_OK) return rc;
+    if ((rc = dt.upload(best_t, n * 64 * sizeof(float))) != RT_OK) return rc;
+    if ((rc = dm.upload(bmax, n * 3 * sizeof(float))) != RT_OK) return rc;
+    if ((rc = db.upload(boxes, n * 32 * 6 * sizeof(float))) != RT_OK) return rc;
+    if ((rc = dout.alloc(n * 32 * sizeof(int32_t))) != RT_OK) return rc;
+    if ((rc = dl.alloc(n * sizeof(int32_t))) != RT_OK) return rc;
+    constexpr int kWaves = BLOCK / 64;
+    hipLaunchKernelGGL(family_test_kernel, dim3((n_waves + kWaves - 1) / kWaves), dim3(BLOCK), 0, nullptr,
+                       static_cast<const float*>(dr.p), active ? static_cast<const uint8_t*>(da.p) : nullptr,
+                       static_cast<const float*>(dt.p), static_cast<const float*>(dm.p), static_cast<const float*>(db.p),
+                       n_waves, static_cast<int32_t*>(dout.p), static_cast<int32_t*>(dl.p));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, n * 32 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_loose, dl.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }

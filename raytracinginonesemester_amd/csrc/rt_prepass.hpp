@@ -12,89 +12,30 @@
 // sc.cut).  SearchBVH only tests a triangle after its ancestors' box tests passed, with tmax =
 // bestT <= FLT_MAX (a smaller tmax only fails more), so such a ray tests no triangle: a miss.
 // Ray directions are positive multiples of D(px,py) = pixel00 + px*du + py*dv - center with
-// px in [x0-0.5, x1+0.5) (jitter), an affine map: its per-component range over the
-// (1-pixel-padded) tile comes from the corners, widened by 1e-5*|D| plus 8 float ulps of every
-// term to cover the float rounding of the per-sample computation (pixel position, difference,
-// cam_unit).  Scaling d by k > 0 scales every slab parameter by 1/k, so "some axis's entry >
-// another axis's exit" is scale-free.  An axis whose component can come near 0
-// (|d_a| < 1e-6 |d|, far above the 1e-8 parallel threshold) is ignored (no constraint):
-// conservative.  A box is missed iff, with 1e-9 relative slack (the reference's doubles carry
-// ~1e-15; the reciprocals below add ~1e-16), some axis's smallest entry exceeds some axis's
-// largest exit, or some axis's largest exit is < 0 (< tmin).  The camera inside a padded box
-// never culls.
-struct TileDirs {
-    double c[3], Dl[3], Dh[3], iDl[3], iDh[3], scale;
-    bool usable;
-};
-__device__ __forceinline__ TileDirs tile_dirs(const RenderParams& P, int x0, int x1, int y0, int y1) {
-    TileDirs T;
-    const double p0[3] = {P.cam_p00.x, P.cam_p00.y, P.cam_p00.z};
-    const double du[3] = {P.cam_du.x, P.cam_du.y, P.cam_du.z};
-    const double dv[3] = {P.cam_dv.x, P.cam_dv.y, P.cam_dv.z};
-    T.c[0] = P.cam_center.x;
-    T.c[1] = P.cam_center.y;
-    T.c[2] = P.cam_center.z;
-    const double pxl = x0 - 1.0, pxh = x1 + 1.0, pyl = y0 - 1.0, pyh = y1 + 1.0;
-    const double pxm = fmax(fabs(pxl), fabs(pxh)), pym = fmax(fabs(pyl), fabs(pyh));
-    T.scale = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double base = p0[a] - T.c[a];
-        const double u0 = pxl * du[a], u1 = pxh * du[a], v0 = pyl * dv[a], v1 = pyh * dv[a];
-        const double ulp = 8.0 * 1.1920928955078125e-7 * (fabs(T.c[a]) + fabs(p0[a]) + pxm * fabs(du[a]) + pym * fabs(dv[a]));
-        T.Dl[a] = base + fmin(u0, u1) + fmin(v0, v1) - ulp;
-        T.Dh[a] = base + fmax(u0, u1) + fmax(v0, v1) + ulp;
-        T.scale = fmax(T.scale, fmax(fabs(T.Dl[a]), fabs(T.Dh[a])));
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        T.Dl[a] -= 1e-5 * T.scale;
-        T.Dh[a] += 1e-5 * T.scale;
-        T.iDl[a] = 1.0 / T.Dl[a];
-        T.iDh[a] = 1.0 / T.Dh[a];
-    }
-    T.usable = T.scale > 0.0;
-    return T;
-}
-
-__device__ __forceinline__ bool tile_misses_box(const TileDirs& T, const float* bx) {
-    const double mn[3] = {bx[0], bx[1], bx[2]}, mx[3] = {bx[3], bx[4], bx[5]};
-    bool inside = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double tol = 1e-6 * (fabs(mn[a]) + fabs(mx[a]) + fabs(T.c[a])) + 1e-30;
-        inside = inside && T.c[a] >= mn[a] - tol && T.c[a] <= mx[a] + tol;
-    }
-    if (inside || !T.usable || !(mn[0] <= mx[0] && mn[1] <= mx[1] && mn[2] <= mx[2])) return false;
-    double entry_min = -INFINITY, exit_max = INFINITY;  // max over axes of min entry; min of max exit
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (!(T.Dl[a] > 1e-6 * T.scale || T.Dh[a] < -1e-6 * T.scale)) continue;  // may be ~parallel
-        const double nA = mn[a] - T.c[a], xA = mx[a] - T.c[a];
-        // d > 0: entry (mn-c)/d, exit (mx-c)/d; d < 0: swapped.  Over d in [Dl, Dh] each
-        // quotient is monotone in d, so its range sits at the endpoints.
-        const double ne = T.Dl[a] > 0 ? nA : xA, nx = T.Dl[a] > 0 ? xA : nA;
-        const double e0 = ne * T.iDl[a], e1 = ne * T.iDh[a];
-        const double f0 = nx * T.iDl[a], f1 = nx * T.iDh[a];
-        entry_min = fmax(entry_min, fmin(e0, e1));
-        exit_max = fmin(exit_max, fmax(f0, f1));
-    }
-    if (!(exit_max == exit_max) || !(entry_min == entry_min)) return false;
-    if (exit_max < -1e-9 * fabs(exit_max) - 1e-30) return true;
-    return entry_min - exit_max > 1e-9 * (fabs(entry_min) + fabs(exit_max)) + 1e-30;
-}
-
-// Float form of tile_dirs / tile_misses_box for tile_cut_kernel (a wave-uniform computation
-// per tile, made 64 times more often than the root test).  Every bound carries its own float
-// rounding on top of the double version's margins: the tile corners are padded by twice the
-// per-sample ulp term (the corner sums are themselves float), and the miss decisions keep a
-// 1e-4 relative slack (the float entry/exit bounds are within ~5 float ulps of the exact
-// quotients), so a culled tile is still one whose every ray fails the reference's double test.
+// px in [x0-0.5, x1+0.5) for the default jitter table, an affine map: its per-component range
+// over the 1-pixel-padded tile comes from the corners, widened by 1.1e-5*|D| plus 16 float ulps
+// of every term: 8 cover the float rounding of the per-sample computation (pixel position,
+// difference, cam_unit), 8 more that of the corner sums, themselves float.  Scaling d by k > 0
+// scales every slab parameter by 1/k, so "some axis's entry > another axis's exit" is
+// scale-free.  An axis whose component can come near 0 (|d_a| < 1e-6 |d|, far above the 1e-8
+// parallel threshold) is ignored (no constraint): conservative.  For d > 0 an axis's entry is
+// (mn-c)/d and its exit (mx-c)/d (d < 0: swapped); over d in [Dl, Dh] each quotient is monotone
+// in d, so its range sits at the endpoints.  A box is missed iff, with 1e-4 relative slack (the
+// float entry/exit bounds are within ~5 float ulps of the exact quotients: v_rcp_f32 is 1 ulp;
+// the reference's doubles carry ~1e-15) and the same slack of the subtractions' operands times
+// the largest |1/D|, some axis's smallest entry exceeds some axis's largest exit, or some axis's
+// largest exit is < 0 (< tmin).  The camera inside a box padded by 1e-4 relative never culls;
+// neither does a box that is inverted or NaN, or coordinates from 1e30 up.
+// The pad is one pixel: it covers sample positions px + j with |j| <= 1 only, so a frame whose
+// jitter table has an entry beyond that, or a non-finite one, runs without the cull
+// (render_frame).  The pair is __host__ __device__ and has one definition: the cull and cut
+// kernels call it, and rt_debug_tile_test_host / _batch run the same text item by item against
+// the rays themselves (tests/tile_cases.py).
 struct TileDirsF {
     float c[3], Dl[3], Dh[3], iDl[3], iDh[3], scale;
     bool usable;
 };
-__device__ __forceinline__ TileDirsF tile_dirs_f(const RenderParams& P, int x0, int x1, int y0, int y1) {
+__host__ __device__ __forceinline__ TileDirsF tile_dirs_f(const RenderParams& P, int x0, int x1, int y0, int y1) {
     TileDirsF T;
     const float p0[3] = {P.cam_p00.x, P.cam_p00.y, P.cam_p00.z};
     const float du[3] = {P.cam_du.x, P.cam_du.y, P.cam_du.z};
@@ -127,7 +68,7 @@ __device__ __forceinline__ TileDirsF tile_dirs_f(const RenderParams& P, int x0, 
     return T;
 }
 
-__device__ __forceinline__ bool tile_misses_box_f(const TileDirsF& T, const float* bx) {
+__host__ __device__ __forceinline__ bool tile_misses_box_f(const TileDirsF& T, const float* bx) {
     const float mn[3] = {bx[0], bx[1], bx[2]}, mx[3] = {bx[3], bx[4], bx[5]};
     bool inside = true;
     float mag = 0.0f, imax = 0.0f;  // magnitude of the subtraction operands, largest |1/D|

@@ -322,6 +322,45 @@ __device__ __forceinline__ void traverse_wave_split(const SceneView& sc, const R
 // about a pixel wide (one reduction of |d - c| around one lane's c, an interval up to twice as
 // wide, took c3 from 0.157 to 0.477 ms).  The reciprocals are v_rcp_f32 (1 ulp; inside the
 // 2^-19 widening of the family test).
+// One axis of the family: the live lanes' interval [dl, dh] (fin: the axis has a bound at all)
+// to the pair U the entry test multiplies by; true when the axis is loose.  The host build and
+// the device build run this text (rt_debug_family_test_host / _batch).
+__host__ __device__ __forceinline__ bool family_axis(float dl, float dh, bool fin, float& u0, float& u1) {
+    const bool ok = (dl >= 1e-8f || dh <= -1e-8f) && fin;
+    const bool lz = !ok && fin;
+    u0 = ok ? rcp_approx(dl) : lz ? (dh > 0.0f ? rcp_approx(dh) : INFINITY) : -INFINITY;
+    u1 = ok ? rcp_approx(dh) : lz ? (dl < 0.0f ? rcp_approx(dl) : -INFINITY) : INFINITY;
+    return lz;
+}
+
+constexpr float kFamilyW = 1.0f / 524288.0f;  // 2^-19: the relative widening of the family test
+
+// The wave-family test of one record entry: box bb (per axis (min, max)), the shared origin o,
+// the family U (family_dirs) and tmax_w, the largest bestT over the live lanes (LOOSE: the wave
+// has a loose axis, U[a] = (ihp, iln) on it).  frustum_loop's test, and the debug entries'.
+template <bool LOOSE>
+__host__ __device__ __forceinline__ bool family_entry_passes(const v2f* bb, const float* o, const v2f* U, float tmax_w) {
+    float nr[3], fr[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const v2f db = bb[a] - (v2f){o[a], o[a]};
+        const v2f p = (v2f){db.x, db.x} * U[a], q = (v2f){db.y, db.y} * U[a];
+        nr[a] = fminf(fminf(p.x, p.y), fminf(q.x, q.y));
+        fr[a] = fmaxf(fmaxf(p.x, p.y), fmaxf(q.x, q.y));
+        if constexpr (LOOSE) {  // U[a] = (ihp, iln) on a loose axis
+            if (U[a].x > 0.0f && U[a].y < 0.0f) {
+                nr[a] = fmaxf(p.x, q.y);
+                fr[a] = INFINITY;
+            }
+        }
+    }
+    float Lc = fmaxf(fmaxf(nr[0], nr[1]), nr[2]);
+    float Hc = fminf(fminf(fr[0], fr[1]), fr[2]);
+    Lc = __builtin_fmaf(fabsf(Lc), -kFamilyW, Lc);
+    Hc = __builtin_fmaf(fabsf(Hc), kFamilyW, Hc);
+    return fmaxf(Lc, kRayTMin) <= fminf(Hc, tmax_w);
+}
+
 __device__ __forceinline__ bool family_dirs(const SceneView& sc, const RayPre& r, bool member, const float* o, v2f* U) {
     const float dd[3] = {r.d.x, r.d.y, r.d.z};
     bool loose = false;  // a loose axis; U = (ihp, iln) on it: U.x > 0 > U.y, which no other axis
@@ -330,13 +369,10 @@ __device__ __forceinline__ bool family_dirs(const SceneView& sc, const RayPre& r
     for (int a = 0; a < 3; ++a) {
         const float dl = wave_reduce_f<false>(member ? dd[a] : INFINITY);
         const float dh = wave_reduce_f<true>(member ? dd[a] : -INFINITY);
-        const bool fin = sc.bmax[a] + fabsf(o[a]) < 1e30f;
-        const bool ok = (dl >= 1e-8f || dh <= -1e-8f) && fin;
-        const bool lz = !ok && fin;
+        float u0, u1;
+        const bool lz = family_axis(dl, dh, sc.bmax[a] + fabsf(o[a]) < 1e30f, u0, u1);
         loose = loose || lz;
         // (made SGPRs: wave-uniform values the VALU computed stay in VGPRs otherwise)
-        const float u0 = ok ? rcp_approx(dl) : lz ? (dh > 0.0f ? rcp_approx(dh) : INFINITY) : -INFINITY;
-        const float u1 = ok ? rcp_approx(dh) : lz ? (dl < 0.0f ? rcp_approx(dl) : -INFINITY) : INFINITY;
         U[a] = (v2f){__int_as_float(uni(__float_as_int(u0))), __int_as_float(uni(__float_as_int(u1)))};
     }
     return loose;
@@ -376,7 +412,6 @@ __device__ __forceinline__ void traverse_frustum(const SceneView& sc, const RayP
 template <bool PK, bool XL, bool QR, bool LOOSE>
 __device__ __forceinline__ void frustum_loop(const SceneView& sc, const RayPre& r, bool live, HitState& hs,
                                              const float* o, const v2f* U) {
-    const float kW = 1.0f / 524288.0f;  // 2^-19
     float tmax_w = FLT_MAX;
     uint32_t ref = sc.root_ref;
     uint32_t st_ref = 0, st_hi = 0;  // lane k holds entry k, st_hi entries 64 + k (FRUSTUM_STACK)
@@ -452,26 +487,8 @@ __device__ __forceinline__ void frustum_loop(const SceneView& sc, const RayPre& 
                 bb[2] = B[2];
                 rk = reinterpret_cast<const uint32_t*>(W)[kref];
             }
-            float nr[3], fr[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const v2f db = bb[a] - (v2f){o[a], o[a]};
-                const v2f p = (v2f){db.x, db.x} * U[a], q = (v2f){db.y, db.y} * U[a];
-                nr[a] = fminf(fminf(p.x, p.y), fminf(q.x, q.y));
-                fr[a] = fmaxf(fmaxf(p.x, p.y), fmaxf(q.x, q.y));
-                if constexpr (LOOSE) {  // U[a] = (ihp, iln) on a loose axis
-                    if (U[a].x > 0.0f && U[a].y < 0.0f) {
-                        nr[a] = fmaxf(p.x, q.y);
-                        fr[a] = INFINITY;
-                    }
-                }
-            }
-            float Lc = fmaxf(fmaxf(nr[0], nr[1]), nr[2]);
-            float Hc = fminf(fminf(fr[0], fr[1]), fr[2]);
-            Lc = __builtin_fmaf(fabsf(Lc), -kW, Lc);
-            Hc = __builtin_fmaf(fabsf(Hc), kW, Hc);
-            const uint32_t m =
-                (uint32_t)ballot(rk != NO_REF && fmaxf(Lc, kRayTMin) <= fminf(Hc, tmax_w)) & ent_mask;
+            const bool pass = family_entry_passes<LOOSE>(bb, o, U, tmax_w);
+            const uint32_t m = (uint32_t)ballot(rk != NO_REF && pass) & ent_mask;
             if (m != 0) {
                 RT_STAT(4, 1);
                 // push the passing entries in record order, hold the last (the reference pops it next)
