@@ -50,7 +50,10 @@ extern "C" {
                                  rt_debug_scene_digest, rt_debug_scene_refit_pack,
                                  rt_debug_scene_refit_chain; rt_scene_rebuild_device, rt_scene_rebuild,
                                  rt_scene_rebuild_path (RT_REBUILD_*), rt_scene_rebuild_counts, rt_build_bvh_triangles,
-                                 rt_debug_box_weight_host, rt_debug_box_weight_batch */
+                                 rt_debug_box_weight_host, rt_debug_box_weight_batch; RT_SORT_ORIGIN,
+                                 RT_SORT_ORIGIN_DIR, rt_scene_bounds, rt_ray_key_bits, rt_ray_keys_host,
+                                 rt_ray_keys_device, rt_ray_sort_host, rt_ray_sort_scratch_bytes,
+                                 rt_ray_sort_device, rt_gather_device, rt_scatter_device */
 
 enum {
     RT_OK = 0,
@@ -950,6 +953,58 @@ int rt_afilm_select_device(rt_afilm* f, const rt_afilm_select_opts* opts, uint32
 int rt_afilm_host(int width, int height, float* sum, uint32_t* count, float* moments, const uint32_t* pixels, size_t m,
                   const float* radiance, int nsamples, float* rgb_out, uint8_t* p6_out, const rt_afilm_select_opts* opts,
                   uint32_t* pixels_out, uint32_t* selected_out);
+
+/* ---- sorting caller rays for coherence: keys, order, gather / scatter ---------------------------
+ * The caller-ray entry points run one ray per lane, and a wave costs what its longest lane costs;
+ * these calls put a batch into an order in which neighbouring lanes start in neighbouring cells of
+ * a box.  A ray's answer does not depend on its lane, so a query on the sorted
+ * batch, scattered back, is the query on the batch, bit for bit.  No call reads a scene: all may
+ * run on any stream beside frames and queries.  Device pointers are on `device`, device calls are
+ * asynchronous on hip_stream (NULL = the null stream), every argument check runs before any HIP
+ * call; n == 0 is RT_OK with no launch (whatever the pointers), n > 2^31-1 is RT_ERR_UNSUPPORTED,
+ * a null argument or a bad mode / bits / elem_bytes is RT_ERR_ARG.
+ *
+ * The key of a ray in a box (lo, hi), with b = bits, all in float, one IEEE operation per
+ * operator in the order written, no contraction:
+ *   cell(x, lo, hi):  t = ((x - lo) / (hi - lo)) * 2^b;  q = t >= 0 ? t : 0  (NaN gives 0);
+ *                     q = q <= 2^b - 1 ? q : 2^b - 1;  the cell is (uint32_t)q.
+ *                     A flat axis gives 0 / 0 -> 0 and x / 0 -> the last cell (the first for x < lo).
+ *   RT_SORT_ORIGIN, b in 1..10: the cells of origin.x, .y, .z; 3b bits.
+ *   RT_SORT_ORIGIN_DIR, b in 1..5: those three, then for the direction d
+ *                     len = sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z),  u = d / len per component,
+ *                     t = ((u + 1.0f) * 0.5f) * 2^b, clamped as above (a zero or non-finite
+ *                     direction is defined: cell 0); 6b bits.
+ *   From the cells' most significant bit down, that bit of each cell in the order listed is
+ *   appended to the key (x leads, as in the LBVH's Morton code).
+ * rt_scene_bounds: the root box the scene holds now (after a refit or rebuild, the new one).
+ * rt_ray_key_bits: 3b or 6b; RT_ERR_ARG for a mode or bits outside the table.
+ * rt_ray_keys_host / rt_ray_keys_device: keys[i] of rays[i]; box is a host pointer in both.
+ * rt_ray_sort_host / rt_ray_sort_device: order = the stable sort of 0..n-1 by key (equal keys keep
+ *   increasing index, so the order is unique); on the device a stable radix sort over exactly
+ *   rt_ray_key_bits bits.  rays_out_dev, when not NULL, receives rays_out[k] = rays[order[k]]; it
+ *   must not overlap rays_dev.  scratch_dev: rt_ray_sort_scratch_bytes(n, mode, bits) bytes, any
+ *   alignment (0 for n == 0, n > 2^31-1 or a bad mode / bits).
+ * rt_gather_device: out[k] = in[order[k]];  rt_scatter_device: out[order[k]] = in[k], for n
+ *   elements of elem_bytes each, a multiple of 4 in 4..64 (indices, t, seeds, max_t, ids: 4;
+ *   radiance: 12; rt_ray: 24; rt_material: 52; rt_hit: 64).  Pointers 4-byte aligned; 16-byte (or
+ *   8-byte) accesses are used when elem_bytes and both addresses allow.  in and out must not
+ *   overlap.  order must be a permutation of 0..n-1, the caller's to keep (as path ids are); an
+ *   entry >= n is skipped, so the calls stay inside their arrays for any order.
+ * (Additive to ABI 3: the names below.) */
+enum { RT_SORT_ORIGIN = 0, RT_SORT_ORIGIN_DIR = 1 };
+int rt_scene_bounds(const rt_scene* s, rt_aabb* out);
+int rt_ray_key_bits(int mode, int bits);
+int rt_ray_keys_host(const rt_ray* rays, size_t n, int mode, int bits, const rt_aabb* box, uint32_t* keys);
+int rt_ray_keys_device(int device, const rt_ray* rays_dev, size_t n, int mode, int bits, const rt_aabb* box,
+                       uint32_t* keys_dev, void* hip_stream);
+int rt_ray_sort_host(const rt_ray* rays, size_t n, int mode, int bits, const rt_aabb* box, uint32_t* order);
+size_t rt_ray_sort_scratch_bytes(size_t n, int mode, int bits);
+int rt_ray_sort_device(int device, const rt_ray* rays_dev, size_t n, int mode, int bits, const rt_aabb* box,
+                       uint32_t* order_dev, rt_ray* rays_out_dev, void* scratch_dev, void* hip_stream);
+int rt_gather_device(int device, const void* in_dev, size_t n, size_t elem_bytes, const uint32_t* order_dev,
+                     void* out_dev, void* hip_stream);
+int rt_scatter_device(int device, const void* in_dev, size_t n, size_t elem_bytes, const uint32_t* order_dev,
+                      void* out_dev, void* hip_stream);
 
 /* The Blinn-Phong powf of the kernels (restatement of the reference libm's powf, see
  * csrc/rt_math.hpp): rt_powf_host evaluates the host build, rt_powf_batch the device build

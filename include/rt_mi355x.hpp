@@ -302,6 +302,48 @@ inline void path_finish(int device, size_t n, float* radiance_dev, void* hip_str
     check(rt_path_finish_device(device, n, radiance_dev, hip_stream));
 }
 
+// Sorting caller rays for coherence (rt_ray_*, rt_gather_device, rt_scatter_device): keys in a box, the stable
+// order by key, and the moves into and out of it.  A query on the sorted rays, scattered back, is the query.
+inline rt_aabb scene_bounds(const DeviceScene& ds) {
+    rt_aabb b;
+    check(rt_scene_bounds(ds.get(), &b));
+    return b;
+}
+inline int ray_key_bits(int mode, int bits) {
+    const int kb = rt_ray_key_bits(mode, bits);
+    if (kb < 0) check(kb);
+    return kb;
+}
+inline std::vector<uint32_t> ray_keys_host(const std::vector<rt_ray>& rays, const rt_aabb& box, int mode, int bits) {
+    std::vector<uint32_t> keys(rays.size());
+    check(rt_ray_keys_host(rays.data(), rays.size(), mode, bits, &box, keys.data()));
+    return keys;
+}
+inline std::vector<uint32_t> ray_sort_host(const std::vector<rt_ray>& rays, const rt_aabb& box, int mode, int bits) {
+    std::vector<uint32_t> order(rays.size());
+    check(rt_ray_sort_host(rays.data(), rays.size(), mode, bits, &box, order.data()));
+    return order;
+}
+inline void ray_keys(int device, const rt_ray* rays_dev, size_t n, int mode, int bits, const rt_aabb& box, uint32_t* keys_dev,
+                     void* hip_stream = nullptr) {
+    check(rt_ray_keys_device(device, rays_dev, n, mode, bits, &box, keys_dev, hip_stream));
+}
+// scratch_dev: rt_ray_sort_scratch_bytes(n, mode, bits) bytes; rays_out_dev may be null.
+inline size_t ray_sort_scratch_bytes(size_t n, int mode, int bits) { return rt_ray_sort_scratch_bytes(n, mode, bits); }
+inline void ray_sort(int device, const rt_ray* rays_dev, size_t n, int mode, int bits, const rt_aabb& box, uint32_t* order_dev,
+                     rt_ray* rays_out_dev, void* scratch_dev, void* hip_stream = nullptr) {
+    check(rt_ray_sort_device(device, rays_dev, n, mode, bits, &box, order_dev, rays_out_dev, scratch_dev, hip_stream));
+}
+// out[k] = in[order[k]] / out[order[k]] = in[k] for n elements of sizeof(T) bytes (a multiple of 4 in 4..64).
+template <class T>
+inline void gather(int device, const T* in_dev, size_t n, const uint32_t* order_dev, T* out_dev, void* hip_stream = nullptr) {
+    check(rt_gather_device(device, in_dev, n, sizeof(T), order_dev, out_dev, hip_stream));
+}
+template <class T>
+inline void scatter(int device, const T* in_dev, size_t n, const uint32_t* order_dev, T* out_dev, void* hip_stream = nullptr) {
+    check(rt_scatter_device(device, in_dev, n, sizeof(T), order_dev, out_dev, hip_stream));
+}
+
 // The step's arithmetic on the host (rt_path_step_host) over host vectors: the state of radiance.size() / 3
 // paths is updated in place; occluded holds rays.size() * lights.size() bytes, entry k's answer for light l at
 // k * lights.size() + l.  ids and mats may be empty (entry k is path k; the table's material of the record).

@@ -33,6 +33,7 @@ RT_REBUILD_NONE, RT_REBUILD_DEVICE, RT_REBUILD_HOST = 0, 1, 2
 RT_PATH_LAST = 16
 RT_PATH_NONE = 0xFFFFFFFF
 RT_PIXEL_NONE = 0xFFFFFFFF
+RT_SORT_ORIGIN, RT_SORT_ORIGIN_DIR = 0, 1
 # rt_tune_id (include/rt_mi355x.h): knob name -> id
 TUNE = {"frustum_arity": 0, "half_waves": 1, "paired_only": 2, "heavy_frac": 3, "heavy_cap": 4,
         "cull_coverage": 5, "cull_boxes": 6, "big_scene_bytes": 7, "frustum_stack_cap": 8,
@@ -271,6 +272,15 @@ SIGNATURES = {
     "rt_afilm_select_scratch_bytes": (SZ, [P]),
     "rt_afilm_select_device": (I, [P, P, P, P, P, P]),
     "rt_afilm_host": (I, [I, I, P, P, P, P, SZ, P, I, P, P, P, P, P]),
+    "rt_scene_bounds": (I, [P, P]),
+    "rt_ray_key_bits": (I, [I, I]),
+    "rt_ray_keys_host": (I, [P, SZ, I, I, P, P]),
+    "rt_ray_keys_device": (I, [I, P, SZ, I, I, P, P, P]),
+    "rt_ray_sort_host": (I, [P, SZ, I, I, P, P]),
+    "rt_ray_sort_scratch_bytes": (SZ, [SZ, I, I]),
+    "rt_ray_sort_device": (I, [I, P, SZ, I, I, P, P, P, P, P]),
+    "rt_gather_device": (I, [I, P, SZ, SZ, P, P, P]),
+    "rt_scatter_device": (I, [I, P, SZ, SZ, P, P, P]),
     "rt_powf_host": (C.c_float, [C.c_float, C.c_float]),
     "rt_debug_frustum_records": (C.c_int, [C.c_size_t, P, P, C.c_int, C.c_int, P, P, C.c_size_t]),
     "rt_debug_scene_pack": (I, [SZ, P, P, P, P, P]),

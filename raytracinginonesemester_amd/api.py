@@ -321,6 +321,18 @@ class DeviceScene:
         check(lib().rt_debug_scene_digest(self._handle(), ptr(info), ptr(dig)))
         return info, dig
 
+    def bounds(self) -> np.ndarray:
+        """The root box the scene holds now, (6,) float32, min corner then max corner
+        (rt_scene_bounds): after a ``refit`` or ``rebuild`` the new one.  The box ``sort=`` uses."""
+        b = L.AABB()
+        check(lib().rt_scene_bounds(self._handle(), C.byref(b)))
+        return np.array([*b.min_corner, *b.max_corner], np.float32)
+
+    def _sorted_rays(self, rays, sort, stream):
+        """(rays in key order, order) for a query's ``sort=`` ("origin", "origin_dir" or True, the
+        measured default) on the device path: the scene's box, the mode's default bits."""
+        return sort_rays(rays, self.bounds(), SORT_DEFAULT if sort is True else sort, None, stream)
+
     @property
     def handle(self) -> C.c_void_p:
         return self._h
@@ -435,7 +447,7 @@ class DeviceScene:
                 "deep": bool(info[3])}
 
     def trace_rays(self, rays, mode: str = "closest", max_t=None, flags: int = 0, stream: Optional[int] = None,
-                   timing: bool = False):
+                   timing: bool = False, sort=None):
         """Batched ray queries against this scene (rt_trace_rays / rt_trace_rays_device): ``rays`` is
         (n, 6) float32, origin then direction, the direction used as given.
 
@@ -447,7 +459,12 @@ class DeviceScene:
         A numpy array takes the host path (upload, trace, download, synchronise; ``timing=True``
         appends the kernel's HIP-event ms).  Torch tensors on the scene's device take the device
         path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no
-        host synchronisation, tensors returned.  ``flags``: RT_FLAG_BINARY or 0."""
+        host synchronisation, tensors returned.  ``flags``: RT_FLAG_BINARY or 0.
+
+        ``sort`` (device path only): "origin", "origin_dir" or True (the measured default) runs the
+        same query on the rays in coherence order (``sort_rays`` in the scene's ``bounds()``, ``max_t``
+        gathered) and scatters the answers back to the caller's order: the same bits, a different
+        assignment of rays to lanes."""
         modes = {"closest": L.RT_RAYS_CLOSEST, "occluded": L.RT_RAYS_OCCLUDED}
         if mode not in modes:
             raise ValueError(f"trace_rays: mode must be one of {sorted(modes)}, not {mode!r}")
@@ -470,12 +487,24 @@ class DeviceScene:
                     raise ValueError("trace_rays: max_t must hold one float per ray")
             if stream is None:
                 stream = torch.cuda.current_stream(dev).cuda_stream
+            order = None
+            if sort is not None and sort is not False and n > 0:
+                rays, order = self._sorted_rays(rays, sort, stream)
+                if mt is not None:
+                    mt = gather(mt, order, stream=stream)
             idx = torch.empty(n, dtype=torch.int32, device=dev)
             t = None if occluded else torch.empty(n, dtype=torch.float32, device=dev)
             check(lib().rt_trace_rays_device(self._handle(), m, rays.data_ptr(), None if mt is None else mt.data_ptr(),
                                              n, int(flags), idx.data_ptr(), None if t is None else t.data_ptr(),
                                              stream))
+            if order is not None:
+                tmp = (rays, order, mt, idx, t)
+                idx = scatter(idx, order, stream=stream)
+                t = None if t is None else scatter(t, order, stream=stream)
+                _used_on(stream, dev, *tmp)
             return idx != 0 if occluded else (idx, t)
+        if sort is not None and sort is not False:
+            raise ValueError("trace_rays: sort is for the device path (torch tensors) only")
         r = _c(rays, np.float32)
         if r.ndim != 2 or r.shape[1] != 6:
             raise ValueError("trace_rays: expects an (n, 6) array of origins and directions")
@@ -498,7 +527,7 @@ class DeviceScene:
         return int(lib().rt_trace_rays_variant(self._handle()))
 
     def shade_rays(self, rays, seeds=None, max_depth: int = 1, diffuse_bounce: bool = True, miss_color=(0, 0, 0),
-                   flags: int = 0, aov: bool = False, stream: Optional[int] = None, timing: bool = False):
+                   flags: int = 0, aov: bool = False, stream: Optional[int] = None, timing: bool = False, sort=None):
         """Radiance of caller rays (rt_shade_rays / rt_shade_rays_device): per ray the reference's
         TraceRayIterative (G/include/query.h:156-220) with ``rng_state = seeds[i]`` (uint32, n; None:
         42 for every ray), bit for bit, the final clamp included.  ``rays`` is (n, 6) float32, origin
@@ -510,7 +539,8 @@ class DeviceScene:
         A numpy array takes the host path (upload, shade, download, synchronise; ``timing=True``
         appends the kernel's HIP-event ms).  Torch tensors on the scene's device take the device
         path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no
-        host synchronisation, tensors returned.  ``flags``: RT_FLAG_BINARY or 0."""
+        host synchronisation, tensors returned.  ``flags``: RT_FLAG_BINARY or 0.  ``sort``: as for
+        trace_rays (rays sorted, ``seeds`` gathered, every output scattered back)."""
         o = L.ShadeOpts()
         o.max_depth, o.diffuse_bounce = int(max_depth), 1 if diffuse_bounce else 0
         o.miss_color = _v3(miss_color)
@@ -538,13 +568,26 @@ class DeviceScene:
                     raise ValueError("shade_rays: seeds must hold one uint32 per ray")
             if stream is None:
                 stream = torch.cuda.current_stream(dev).cuda_stream
+            order = None
+            if sort is not None and sort is not False and n > 0:
+                rays, order = self._sorted_rays(rays, sort, stream)
+                if sd is not None:
+                    sd = gather(sd.view(torch.int32), order, stream=stream)
             rad = torch.empty((n, 3), dtype=torch.float32, device=dev)
             idx = torch.empty(n, dtype=torch.int32, device=dev) if aov else None
             t = torch.empty(n, dtype=torch.float32, device=dev) if aov else None
             check(lib().rt_shade_rays_device(self._handle(), rays.data_ptr(), None if sd is None else sd.data_ptr(), n,
                                              C.byref(o), rad.data_ptr(), None if idx is None else idx.data_ptr(),
                                              None if t is None else t.data_ptr(), stream))
+            if order is not None:
+                tmp = (rays, order, sd, rad, idx, t)
+                rad = scatter(rad, order, stream=stream)
+                if aov:
+                    idx, t = scatter(idx, order, stream=stream), scatter(t, order, stream=stream)
+                _used_on(stream, dev, *tmp)
             return (rad, idx, t) if aov else rad
+        if sort is not None and sort is not False:
+            raise ValueError("shade_rays: sort is for the device path (torch tensors) only")
         r = _c(rays, np.float32)
         if r.ndim != 2 or r.shape[1] != 6:
             raise ValueError("shade_rays: expects an (n, 6) array of origins and directions")
@@ -681,7 +724,7 @@ class DeviceScene:
             if own:
                 film.close()
 
-    def trace_hits(self, rays, flags: int = 0, stream: Optional[int] = None, timing: bool = False):
+    def trace_hits(self, rays, flags: int = 0, stream: Optional[int] = None, timing: bool = False, sort=None):
         """Hit records of caller rays (rt_trace_hits / rt_trace_hits_device): per ray the HitRecord
         SearchBVH returns (G/include/query.h:224-311, intersectTriangle's tail :110-130) with the ids
         assignMaterialToHit reads, bit for bit.  ``rays`` is (n, 6) float32, origin then direction,
@@ -692,7 +735,8 @@ class DeviceScene:
         appends the kernel's HIP-event ms).  A torch tensor on the scene's device takes the device
         path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no host
         synchronisation, and one (n, 16) int32 tensor is returned, the records' 32-bit words
-        (hit_fields names them).  ``flags``: RT_FLAG_BINARY or 0."""
+        (hit_fields names them).  ``flags``: RT_FLAG_BINARY or 0.  ``sort``: as for trace_rays (rays
+        sorted, the records scattered back)."""
         if type(rays).__module__.split(".")[0] == "torch":
             import torch
 
@@ -705,9 +749,18 @@ class DeviceScene:
             n = rays.shape[0]
             if stream is None:
                 stream = torch.cuda.current_stream(dev).cuda_stream
+            order = None
+            if sort is not None and sort is not False and n > 0:
+                rays, order = self._sorted_rays(rays, sort, stream)
             hits = torch.empty((n, 16), dtype=torch.int32, device=dev)
             check(lib().rt_trace_hits_device(self._handle(), rays.data_ptr(), n, int(flags), hits.data_ptr(), stream))
+            if order is not None:
+                tmp = (rays, order, hits)
+                hits = scatter(hits, order, stream=stream)
+                _used_on(stream, dev, *tmp)
             return hits
+        if sort is not None and sort is not False:
+            raise ValueError("trace_hits: sort is for the device path (torch tensors) only")
         r = _c(rays, np.float32)
         if r.ndim != 2 or r.shape[1] != 6:
             raise ValueError("trace_hits: expects an (n, 6) array of origins and directions")
@@ -796,7 +849,7 @@ class DeviceScene:
         return int(lib().rt_path_step_variant(self._handle()))
 
     def trace_paths(self, rays, seeds=None, max_depth: int = 1, diffuse_bounce: bool = True, miss_color=(0, 0, 0),
-                    material_fn=None, compact: bool = True, flags: int = 0):
+                    material_fn=None, compact: bool = True, flags: int = 0, sort=None):
         """Radiance of caller rays by stages, on torch's current stream: path_begin, then per depth
         trace_hits -> ``material_fn`` -> path_step -> compact_paths, then path_finish.  With
         ``material_fn=None`` the result is shade_rays' bit for bit.
@@ -807,7 +860,13 @@ class DeviceScene:
         for the scene's table.  ``compact``: the live rays are packed after every depth (one read
         of their count, the one synchronisation per depth); without it every depth runs all n
         entries, the ended ones as no path.  The last depth's step is issued with RT_PATH_LAST;
-        ``max_depth <= 0`` returns zeros without a launch.  Returns (n, 3) float32, clamped."""
+        ``max_depth <= 0`` returns zeros without a launch.  Returns (n, 3) float32, clamped.
+
+        ``sort`` ("origin", "origin_dir" or True, the measured default): before each depth's
+        trace_hits, after the compaction, the current rays and their ids are put into coherence
+        order (``sort_rays`` in the scene's ``bounds()``; the ids become the order at the first
+        depth).  Nothing is scattered back, the state being indexed by id; ``material_fn`` sees the
+        sorted entries with their ids.  The result is the same, bit for bit."""
         import torch
 
         dev = self._torch_dev()
@@ -818,8 +877,14 @@ class DeviceScene:
             return torch.zeros((n, 3), dtype=torch.float32, device=dev)
         state = self.path_begin(n, seeds)
         cur, ids = rays.contiguous(), None
+        if sort is False:
+            sort = None
+        box = None if sort is None else self.bounds()
         for depth in range(int(max_depth)):
             last = depth + 1 == int(max_depth)
+            if sort is not None:
+                cur, order = sort_rays(cur, box, SORT_DEFAULT if sort is True else sort)
+                ids = order if ids is None else gather(ids, order)
             hits = self.trace_hits(cur, flags)
             mats = None
             if material_fn is not None:
@@ -1618,6 +1683,20 @@ def _stream_of(stream, dev):
     return torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
 
 
+def _used_on(stream, dev, *tensors) -> None:
+    """Tell torch's allocator that ``tensors``, temporaries a call drops on return, are in use on
+    ``stream`` (a HIP stream handle) when that is not torch's current stream, so that their memory
+    is not handed out again before the launches on it have run."""
+    import torch
+
+    if stream is None or stream == torch.cuda.current_stream(dev).cuda_stream:
+        return
+    ext = torch.cuda.ExternalStream(stream, device=dev)
+    for t in tensors:
+        if t is not None:
+            t.record_stream(ext)
+
+
 def _seed_tensor(seeds, n: int, dev, who: str):
     """n uint32 seeds as an int32 tensor on dev (the same 32 bits), or None."""
     import torch
@@ -1685,6 +1764,141 @@ def compact_paths(alive, rays, ids=None, stream: Optional[int] = None):
         torch.cuda.ExternalStream(st, device=dev).synchronize()
     c = int(count.item())
     return out_r[:c], out_i[:c], c
+
+
+# ---- sorting caller rays for coherence (rt_ray_*, rt_gather_device, rt_scatter_device) ---------------
+SORT_MODES = {"origin": L.RT_SORT_ORIGIN, "origin_dir": L.RT_SORT_ORIGIN_DIR}
+SORT_MAX_BITS = {"origin": 10, "origin_dir": 5}
+# The bits a mode takes when none are given: per mode the sweep's lowest total of sort + query +
+# scatter over the frog batches of classes B and C (profiles/r10/ray_sort.jsonl).
+# ``sort=True`` is the lower of the two: origin at 8 bits.
+SORT_DEFAULT_BITS = {"origin": 8, "origin_dir": 5}
+SORT_DEFAULT = "origin"
+
+
+def _sort_spec(mode, bits, who: str):
+    """(RT_SORT_* id, bits) of a mode name (True: the default mode) and bits (None: the mode's default)."""
+    if mode is True:
+        mode = SORT_DEFAULT
+    if mode not in SORT_MODES:
+        raise ValueError(f"{who}: sort mode must be one of {sorted(SORT_MODES)} (or True), not {mode!r}")
+    b = SORT_DEFAULT_BITS[mode] if bits is None else int(bits)
+    if not 1 <= b <= SORT_MAX_BITS[mode]:
+        raise ValueError(f"{who}: bits must be in 1..{SORT_MAX_BITS[mode]} for mode {mode!r}")
+    return SORT_MODES[mode], b
+
+
+def _aabb(box, who: str) -> L.AABB:
+    b = np.asarray(box, np.float32).reshape(-1)
+    if b.size != 6:
+        raise ValueError(f"{who}: box must hold 6 floats (min corner, max corner)")
+    return L.AABB(_v3(b[:3]), _v3(b[3:]))
+
+
+def _is_torch(a) -> bool:
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _ray_tensor(rays, who: str):
+    import torch
+
+    if rays.device.type != "cuda" or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
+        raise ValueError(f"{who}: expects an (n, 6) float32 tensor on a device")
+    return rays.contiguous()
+
+
+def ray_key_bits(mode="origin", bits=None) -> int:
+    """Bits of a mode's key (rt_ray_key_bits): 3 * bits (origin) or 6 * bits (origin_dir)."""
+    m, b = _sort_spec(mode, bits, "ray_key_bits")
+    return int(lib().rt_ray_key_bits(m, b))
+
+
+def ray_keys(rays, box, mode="origin", bits=None, stream: Optional[int] = None):
+    """Coherence keys of caller rays in ``box`` (6 floats, min then max corner; DeviceScene.bounds
+    gives a scene's): per ray the interleaved cells of its origin on a 2^bits grid over the box
+    (``mode="origin"``, bits 1..10) or of its origin and unit direction (``"origin_dir"``, bits
+    1..5), in exact float32 (include/rt_mi355x.h states the arithmetic).  A numpy (n, 6) array takes
+    the host build and returns uint32; a torch tensor takes the kernel on ``stream`` (default torch's
+    current stream) and returns an int32 tensor with the same bits."""
+    m, b = _sort_spec(mode, bits, "ray_keys")
+    bx = _aabb(box, "ray_keys")
+    if _is_torch(rays):
+        import torch
+
+        r = _ray_tensor(rays, "ray_keys")
+        n = r.shape[0]
+        keys = torch.empty(n, dtype=torch.int32, device=r.device)
+        check(lib().rt_ray_keys_device(r.device.index, r.data_ptr(), n, m, b, C.byref(bx), keys.data_ptr(),
+                                       _stream_of(stream, r.device)))
+        return keys
+    r = _c(rays, np.float32)
+    if r.ndim != 2 or r.shape[1] != 6:
+        raise ValueError("ray_keys: expects an (n, 6) array of origins and directions")
+    keys = np.zeros(r.shape[0], np.uint32)
+    check(lib().rt_ray_keys_host(ptr(r), r.shape[0], m, b, C.byref(bx), ptr(keys)))
+    return keys
+
+
+def sort_rays(rays, box, mode="origin", bits=None, stream: Optional[int] = None):
+    """Rays in key order (rt_ray_sort_device / rt_ray_sort_host): returns ``(sorted_rays, order)``,
+    ``order`` (n,) int32 the stable sort of the indices by ``ray_keys`` (equal keys keep increasing
+    index), ``sorted_rays[k] = rays[order[k]]``.  A torch tensor is sorted on its device on ``stream``
+    (default torch's current stream), with no host synchronisation; a numpy array on the host."""
+    m, b = _sort_spec(mode, bits, "sort_rays")
+    bx = _aabb(box, "sort_rays")
+    if _is_torch(rays):
+        import torch
+
+        r = _ray_tensor(rays, "sort_rays")
+        n = r.shape[0]
+        out = torch.empty_like(r)
+        order = torch.empty(n, dtype=torch.int32, device=r.device)
+        if n > 0:
+            scratch = torch.empty(int(lib().rt_ray_sort_scratch_bytes(n, m, b)), dtype=torch.uint8, device=r.device)
+            check(lib().rt_ray_sort_device(r.device.index, r.data_ptr(), n, m, b, C.byref(bx), order.data_ptr(),
+                                           out.data_ptr(), scratch.data_ptr(), _stream_of(stream, r.device)))
+            _used_on(stream, r.device, scratch)
+        return out, order
+    r = _c(rays, np.float32)
+    if r.ndim != 2 or r.shape[1] != 6:
+        raise ValueError("sort_rays: expects an (n, 6) array of origins and directions")
+    order = np.zeros(r.shape[0], np.uint32)
+    check(lib().rt_ray_sort_host(ptr(r), r.shape[0], m, b, C.byref(bx), ptr(order)))
+    return r[order], order.view(np.int32)
+
+
+def _permute(fn, who: str, x, order, out, stream):
+    import torch
+
+    if not _is_torch(x) or x.device.type != "cuda" or x.dim() < 1 or not x.is_contiguous():
+        raise ValueError(f"{who}: expects a contiguous device tensor with one row per entry")
+    n = x.shape[0]
+    eb = x.element_size()
+    for d in x.shape[1:]:
+        eb *= int(d)
+    if eb % 4 != 0 or not 4 <= eb <= 64:
+        raise ValueError(f"{who}: a row must hold a multiple of 4 bytes in 4..64, not {eb}")
+    if order.device != x.device or order.dtype != torch.int32 or tuple(order.shape) != (n,) or not order.is_contiguous():
+        raise ValueError(f"{who}: order must be a contiguous (n,) int32 tensor on the entries' device")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.device != x.device or out.dtype != x.dtype or out.shape != x.shape or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous tensor like the input")
+    if n > 0:
+        check(fn(x.device.index, x.data_ptr(), n, eb, order.data_ptr(), out.data_ptr(), _stream_of(stream, x.device)))
+    return out
+
+
+def gather(x, order, out=None, stream: Optional[int] = None):
+    """``out[k] = x[order[k]]`` on the device (rt_gather_device): ``x`` a contiguous tensor whose rows
+    hold 4..64 bytes (a multiple of 4), ``order`` (n,) int32, a permutation of 0..n-1.  One launch
+    on ``stream`` (default torch's current stream); returns ``out`` (a new tensor unless given)."""
+    return _permute(lib().rt_gather_device, "gather", x, order, out, stream)
+
+
+def scatter(x, order, out=None, stream: Optional[int] = None):
+    """``out[order[k]] = x[k]`` on the device (rt_scatter_device), the inverse of ``gather``."""
+    return _permute(lib().rt_scatter_device, "scatter", x, order, out, stream)
 
 
 def path_step_host(rays, hits, radiance, throughput, rng, occluded, lights, table=None, materials=None, ids=None,

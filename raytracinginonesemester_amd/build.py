@@ -8,7 +8,8 @@
   its device code in the rt_wave/instrument/traverse/shade/prepass/query/path/refit/rebuild.hpp sections),
   rt_hw1.hip (the HW1 path),
   rt_frame.hip (P6 quantisation, strip un-permute, the film and the adaptive film on the device), rt_lbvh.hip (LBVH build on
-  the device), rt_renderer.hip (the multi-GPU frame renderer).  Units compile in parallel.
+  the device), rt_renderer.hip (the multi-GPU frame renderer), rt_raysort.hip (ray keys, the
+  stable sort by key, gather / scatter; its key in rt_raysort.hpp).  Units compile in parallel.
   Every float path is compiled with -ffp-contract=off and without fast-math; HIP's default
   correctly rounded f32 division / sqrt stay on (parity with the reference CPU build).
 * rt_render_cli   — C++ CLI over the C ABI (scene JSON in, P6 out), G/src/main.cu's role.
@@ -38,7 +39,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
 FP = ["-ffp-contract=off", "-fno-fast-math"]
-DEVICE_UNITS = ["rt_device", "rt_hw1", "rt_frame", "rt_lbvh", "rt_renderer"]
+DEVICE_UNITS = ["rt_device", "rt_hw1", "rt_frame", "rt_lbvh", "rt_renderer", "rt_raysort"]
 HOST_UNITS = ["rt_host", "rt_records", "rt_scene_pack"]
 
 

@@ -1597,6 +1597,13 @@ extern "C" void rt_scene_destroy(rt_scene* s) {
 }
 extern "C" int rt_scene_device(const rt_scene* s) { return s ? s->device : -1; }
 
+// The root box the scene holds now (a refit or rebuild replaces it): the box rt_ray_sort_* take.
+extern "C" int rt_scene_bounds(const rt_scene* s, rt_aabb* out) {
+    if (!s || !out) return set_error(RT_ERR_ARG, "rt_scene_bounds: null argument");
+    std::memcpy(out, s->root_box, sizeof(rt_aabb));
+    return RT_OK;
+}
+
 extern "C" int rt_scene_traversal_info(const rt_scene* s, int64_t info[4]) {
     if (!s || !info) return set_error(RT_ERR_ARG, "rt_scene_traversal_info: null argument");
     const bool frustum = s->wide && !s->deep;
