@@ -53,7 +53,9 @@ extern "C" {
                                  rt_debug_box_weight_host, rt_debug_box_weight_batch; RT_SORT_ORIGIN,
                                  RT_SORT_ORIGIN_DIR, rt_scene_bounds, rt_ray_key_bits, rt_ray_keys_host,
                                  rt_ray_keys_device, rt_ray_sort_host, rt_ray_sort_scratch_bytes,
-                                 rt_ray_sort_device, rt_gather_device, rt_scatter_device */
+                                 rt_ray_sort_device, rt_gather_device, rt_scatter_device; rt_multi_hit,
+                                 RT_MULTI_HIT_MAX_K, rt_trace_multi_hits, rt_trace_multi_hits_device,
+                                 rt_trace_multi_hits_variant, rt_multi_hits_host */
 
 enum {
     RT_OK = 0,
@@ -708,6 +710,78 @@ int rt_trace_hits_variant(const rt_scene* s);
  * intersectTriangle(rays[i], tris[i], 1e-4f, FLT_MAX) as a full record, through the functions the
  * kernel runs.  tri = i on a hit, object_id = material = -1; a miss record otherwise. */
 int rt_hit_record_host(const rt_ray* rays, const rt_triangle* tris, int n, rt_hit* out);
+
+/* ---- multi-hit queries on a resident scene ---------------------------------------------------
+ * Every surface along a caller ray, not only the first: the number of triangles
+ * the ray hits up to a bound, and the k nearest of them in order — alpha cut-outs and transparent
+ * shadow rays, thickness and X-ray images, inside/outside tests by crossing parity, depth-ordered
+ * surface lists.
+ *
+ * For a ray (origin, direction) and a bound tmax (max_t[i]; FLT_MAX when max_t is NULL) the hit
+ * set S is what SearchBVH (G/include/query.h:224-311) would collect if
+ *   - the bound it passes to intersectAABB and intersectTriangle stayed at tmax and were never
+ *     lowered to a hit,
+ *   - every accepted triangle were kept, not only the last one,
+ *   - the direction is used as given and tmin = 1e-4, as in every query here.
+ * Without stack overflow S is the set of triangles for which every box on the root-to-leaf path,
+ *   the root's own and the leaf's own included, passes intersectAABB(ray, box, 1e-4, tmax) and
+ *   intersectTriangle(ray, tri, 1e-4, tmax) accepts (t <= tmax counts).  A leaf that names no
+ *   triangle contributes nothing.  With one bound the push-time and pop-time tests of a box agree
+ *   and the order of the visit does not matter.  (A triangle is counted once per leaf that names it.)
+ * With stack overflow the rule follows the reference's 512-entry stack: SearchBVH pops a node,
+ *   tests its own box, then pushes left and right when their boxes pass; if that control flow, run
+ *   with the fixed bound, would set its overflow flag for this ray, S is instead every triangle of
+ *   the scene that intersectTriangle(ray, tri, 1e-4, tmax) accepts: the reference's brute-force
+ *   completion, a superset of what the DFS saw.  Whether a ray overflows is a deterministic
+ *   property of the tree, the ray and tmax.
+ * Outputs per ray: count[i] = |S|, the full number of hits, which may exceed k; hits[i*k + j] for
+ *   j < min(|S|, k) are the first members of S by ascending t, then by ascending triangle index,
+ *   each with intersectTriangle's t, u, v bit for bit (the t, u, v rt_hit has for that triangle);
+ *   slots j >= |S| get tri = -1, t = -1.0f, u = v = 0.  Every byte of hits[i*k .. i*k + k-1] and of
+ *   count[i] is written.
+ * Nothing is pruned by the k-th distance: count would lose its meaning, and a float box test
+ *   cannot prove a subtree empty of closer hits exactly.
+ * Always true: the reference's closest hit is a member of S (its boxes passed with a smaller bound,
+ *   and the slab test is monotone in tmax), count > 0 exactly when SearchBVH hits (with max_t NULL),
+ *   and hits[0].t <= the closest-hit query's t.
+ * Arguments: 0 <= k <= RT_MULTI_HIT_MAX_K.  With k == 0 only the counts are produced and hits may
+ *   be NULL; with k > 0 count may be NULL.  RT_ERR_ARG: a null scene or rays, k out of range, no
+ *   output (k == 0 with a null count, k > 0 with null hits), a hits_dev that is not 16-byte aligned
+ *   (the kernel stores 16-byte words; the host entry's `hits` needs no alignment), a flag bit other
+ *   than RT_FLAG_BINARY.  n == 0 is RT_OK with no launch; n > 2^31-1 or n*k > 2^31-1 is
+ *   RT_ERR_UNSUPPORTED.  Every argument check runs before any HIP call.
+ * For any float bit patterns in rays and max_t the call terminates and writes every output; the
+ *   results are specified for finite rays and a max_t that is not NaN.
+ * Like the other queries it reads only the scene's current packed arrays (after rt_scene_refit /
+ * rt_scene_rebuild: the new ones) and takes no part in the frame ordering: any stream, any thread,
+ * beside frames of the same scene, of a clone or of an rt_renderer's scene.
+ * (Additive to ABI 3: rt_multi_hit, RT_MULTI_HIT_MAX_K, rt_trace_multi_hits,
+ * rt_trace_multi_hits_device, rt_trace_multi_hits_variant, rt_multi_hits_host.) */
+typedef struct {            /* 16 bytes */
+    int32_t tri;            /* triangle index; -1: no such hit */
+    float   t, u, v;        /* intersectTriangle's t, u, v (query.h:92-104) */
+} rt_multi_hit;
+#define RT_MULTI_HIT_MAX_K 32
+
+/* Asynchronous on hip_stream (NULL = the null stream); device pointers on the scene's device:
+ * rays_dev n rt_ray, max_t_dev n floats (or NULL), hits_dev n*k rt_multi_hit (16-byte aligned; may
+ * be NULL with k == 0), count_dev n (may be NULL with k > 0). */
+int rt_trace_multi_hits_device(rt_scene* s, const rt_ray* rays_dev, const float* max_t_dev, size_t n, int k, int flags,
+                               rt_multi_hit* hits_dev, int32_t* count_dev, void* hip_stream);
+/* Host arrays; uploads, traces, downloads, synchronises.  kernel_ms (may be NULL): HIP-event time
+ * of the kernel. */
+int rt_trace_multi_hits(rt_scene* s, const rt_ray* rays, const float* max_t, size_t n, int k, int flags,
+                        rt_multi_hit* hits, int32_t* count, float* kernel_ms);
+/* RT_RAYS_VARIANT_* of the latest rt_trace_multi_hits[_device] call on s (NONE before the first),
+ * by rt_trace_rays_variant's rule; a word of its own, which the other queries do not write. */
+int rt_trace_multi_hits_variant(const rt_scene* s);
+/* The host build of the query (no device needed): the definition above, the overflow rule
+ * included, on arrays in the reference layout (P triangles, 2P-1 nodes and boxes, the root node
+ * 0), through the box and triangle tests the kernel runs.  max_t, hits and count as for
+ * rt_trace_multi_hits.  A child index outside the node array, or nodes that are not a tree, are
+ * RT_ERR_ARG. */
+int rt_multi_hits_host(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                       const rt_ray* rays, const float* max_t, size_t n, int k, rt_multi_hit* hits, int32_t* count);
 
 /* Camera rays of image rows [row0, row0 + rows): the rays render() shoots and the rng states it
  * gives them (G/include/query.cu:146-158), for rt_trace_rays / rt_trace_hits / rt_shade_rays.  The

@@ -34,6 +34,7 @@ RT_PATH_LAST = 16
 RT_PATH_NONE = 0xFFFFFFFF
 RT_PIXEL_NONE = 0xFFFFFFFF
 RT_SORT_ORIGIN, RT_SORT_ORIGIN_DIR = 0, 1
+RT_MULTI_HIT_MAX_K = 32
 # rt_tune_id (include/rt_mi355x.h): knob name -> id
 TUNE = {"frustum_arity": 0, "half_waves": 1, "paired_only": 2, "heavy_frac": 3, "heavy_cap": 4,
         "cull_coverage": 5, "cull_boxes": 6, "big_scene_bytes": 7, "frustum_stack_cap": 8,
@@ -242,6 +243,10 @@ SIGNATURES = {
     "rt_trace_hits": (I, [P, P, SZ, I, P, P]),
     "rt_trace_hits_variant": (I, [P]),
     "rt_hit_record_host": (I, [P, P, I, P]),
+    "rt_trace_multi_hits_device": (I, [P, P, P, SZ, I, I, P, P, P]),
+    "rt_trace_multi_hits": (I, [P, P, P, SZ, I, I, P, P, P]),
+    "rt_trace_multi_hits_variant": (I, [P]),
+    "rt_multi_hits_host": (I, [SZ, P, P, P, P, P, SZ, I, P, P]),
     "rt_camera_rays_host": (I, [P, I, P, I, I, P, P]),
     "rt_camera_rays_device": (I, [I, P, I, P, I, I, P, P, P]),
     "rt_camera_rays_pass_host": (I, [P, I, I, P, I, I, P, P]),

@@ -34,6 +34,9 @@ assert C.sizeof(L.Material) == 52 and C.sizeof(L.Triangle) == 72 and C.sizeof(L.
 HIT_DTYPE = np.dtype([("tri", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("p", "<f4", 3), ("normal", "<f4", 3),
                       ("geom_normal", "<f4", 3), ("front_face", "<i4"), ("object_id", "<i4"), ("material", "<i4")])
 assert HIT_DTYPE.itemsize == C.sizeof(L.Hit) == 64
+# rt_multi_hit: one list entry of DeviceScene.trace_multi_hits
+MULTI_HIT_DTYPE = np.dtype([("tri", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4")])
+assert MULTI_HIT_DTYPE.itemsize == 16
 
 
 def _v3(v) -> L.Vec3:
@@ -774,6 +777,79 @@ class DeviceScene:
         """The traversal the latest trace_hits call launched (RT_RAYS_VARIANT_*)."""
         return int(lib().rt_trace_hits_variant(self._handle()))
 
+    def trace_multi_hits(self, rays, k: int, max_t=None, flags: int = 0, stream: Optional[int] = None,
+                         timing: bool = False):
+        """Every hit along caller rays (rt_trace_multi_hits / rt_trace_multi_hits_device): per ray
+        the number of triangles it hits in [1e-4, max_t] (``max_t`` n float32; None: FLT_MAX) and the
+        ``k`` nearest of them (0 <= k <= RT_MULTI_HIT_MAX_K) by ascending t, then triangle index.
+        Nothing stops at the first surface and nothing is pruned: the hit set is SearchBVH's
+        (G/include/query.h:224-311) with the bound held at max_t, its overflow rule included.
+
+        Returns ``(count, tri, t, u, v)``: ``count`` (n,) int32, the full number of hits (it may
+        exceed k); ``tri`` (n, k) int32 and ``t``, ``u``, ``v`` (n, k) float32, intersectTriangle's
+        values bit for bit, -1 / -1.0 / 0 / 0 in the slots past ``count``.
+
+        A numpy array takes the host path (upload, trace, download, synchronise; ``timing=True``
+        appends the kernel's HIP-event ms).  Torch tensors on the scene's device take the device
+        path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no
+        host synchronisation, tensors returned (views of one (n, k, 4) record tensor).  ``flags``:
+        RT_FLAG_BINARY or 0."""
+        k = int(k)
+        if not 0 <= k <= L.RT_MULTI_HIT_MAX_K:
+            raise ValueError(f"trace_multi_hits: k must be in 0..{L.RT_MULTI_HIT_MAX_K}")
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
+                raise ValueError(f"trace_multi_hits: expects an (n, 6) float32 tensor on {dev}")
+            if timing:
+                raise ValueError("trace_multi_hits: timing is measured on the host path only")
+            rays = rays.contiguous()
+            n = rays.shape[0]
+            mt = None
+            if max_t is not None:
+                mt = torch.as_tensor(max_t, dtype=torch.float32, device=dev).contiguous()
+                if mt.shape != (n,):
+                    raise ValueError("trace_multi_hits: max_t must hold one float per ray")
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+            rec = torch.empty((n, k, 4), dtype=torch.int32, device=dev)
+            if n > 0:  # (an empty tensor has no address to pass)
+                check(lib().rt_trace_multi_hits_device(self._handle(), rays.data_ptr(), None if mt is None else mt.data_ptr(),
+                                                       n, k, int(flags), rec.data_ptr() if k > 0 else None,
+                                                       count.data_ptr(), stream))
+            _used_on(stream, dev, rays, mt)
+            f = rec.view(torch.float32)
+            return count, rec[:, :, 0], f[:, :, 1], f[:, :, 2], f[:, :, 3]
+        r = _c(rays, np.float32)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("trace_multi_hits: expects an (n, 6) array of origins and directions")
+        n = r.shape[0]
+        mt = None
+        if max_t is not None:
+            mt = _c(max_t, np.float32)
+            if mt.shape != (n,):
+                raise ValueError("trace_multi_hits: max_t must hold one float per ray")
+        count = np.zeros(n, np.int32)
+        rec = np.zeros((n, k), MULTI_HIT_DTYPE)
+        ms = C.c_float(0.0)
+        check(lib().rt_trace_multi_hits(self._handle(), ptr(r), ptr(mt), n, k, int(flags), ptr(rec) if k > 0 else None,
+                                        ptr(count), C.byref(ms) if timing else None))
+        out = (count, rec["tri"], rec["t"], rec["u"], rec["v"])
+        return (*out, ms.value) if timing else out
+
+    def count_hits(self, rays, max_t=None, flags: int = 0, stream: Optional[int] = None, timing: bool = False):
+        """The number of triangles each ray hits in [1e-4, max_t]: trace_multi_hits with k = 0, which
+        keeps no list.  Returns ``count`` (n,) int32 (``timing=True`` on the host path: ``(count, ms)``)."""
+        out = self.trace_multi_hits(rays, 0, max_t=max_t, flags=flags, stream=stream, timing=timing)
+        return (out[0], out[-1]) if timing else out[0]
+
+    def multi_hits_variant(self) -> int:
+        """The traversal the latest trace_multi_hits / count_hits call launched (RT_RAYS_VARIANT_*)."""
+        return int(lib().rt_trace_multi_hits_variant(self._handle()))
+
     # ---- path stages for caller hits (rt_path_*) ------------------------------------------------
     def _torch_dev(self):
         import torch
@@ -1209,6 +1285,34 @@ def hit_record_host(rays, tris) -> np.ndarray:
     out = np.zeros(r.shape[0], HIT_DTYPE)
     check(lib().rt_hit_record_host(ptr(r), ptr(t), r.shape[0], ptr(out)))
     return out
+
+
+def multi_hits_host(nodes, aabbs, triangles, rays, k: int, max_t=None):
+    """Host build of DeviceScene.trace_multi_hits (rt_multi_hits_host, no device) on arrays in the
+    reference layout: ``nodes`` (2P-1, 4) uint32, ``aabbs`` (2P-1, 6), ``triangles`` (P, 18), ``rays``
+    (n, 6) float32, ``max_t`` (n,) float32 or None (FLT_MAX).  The reference's 512-entry stack and
+    its overflow rule included.  Returns ``(count, tri, t, u, v)`` as the numpy path of
+    trace_multi_hits does."""
+    nd, bx, tr, r = _c(nodes, np.uint32), _c(aabbs, np.float32), _c(triangles, np.float32), _c(rays, np.float32)
+    P = tr.size // 18
+    k = int(k)
+    if P == 0 or nd.size != 4 * (2 * P - 1) or bx.size != 6 * (2 * P - 1):
+        raise ValueError("multi_hits_host: expects 2P-1 nodes and boxes for P >= 1 triangles")
+    if r.ndim != 2 or r.shape[1] != 6:
+        raise ValueError("multi_hits_host: expects an (n, 6) array of origins and directions")
+    if not 0 <= k <= L.RT_MULTI_HIT_MAX_K:
+        raise ValueError(f"multi_hits_host: k must be in 0..{L.RT_MULTI_HIT_MAX_K}")
+    n = r.shape[0]
+    mt = None
+    if max_t is not None:
+        mt = _c(max_t, np.float32)
+        if mt.shape != (n,):
+            raise ValueError("multi_hits_host: max_t must hold one float per ray")
+    count = np.zeros(n, np.int32)
+    rec = np.zeros((n, k), MULTI_HIT_DTYPE)
+    check(lib().rt_multi_hits_host(P, ptr(nd), ptr(bx), ptr(tr), ptr(r), ptr(mt), n, k, ptr(rec) if k > 0 else None,
+                                   ptr(count)))
+    return count, rec["tri"], rec["t"], rec["u"], rec["v"]
 
 
 # rt_hit's 32-bit words by field: (first word, words, float)

@@ -195,6 +195,7 @@ struct RenderParams {
 #include "rt_shade.hpp"
 #include "rt_prepass.hpp"
 #include "rt_query.hpp"
+#include "rt_multihit.hpp"
 #include "rt_path.hpp"
 #include "rt_refit.hpp"
 #include "rt_rebuild.hpp"
@@ -734,6 +735,8 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     std::atomic<int> hits_variant{RT_RAYS_VARIANT_NONE};
     // ... and of the latest rt_path_step_device call
     std::atomic<int> path_variant{RT_RAYS_VARIANT_NONE};
+    // ... and of the latest rt_trace_multi_hits[_device] call
+    std::atomic<int> multi_variant{RT_RAYS_VARIANT_NONE};
     DevBuf inode, wnode, ibox, leaf, tnorm, objids, mats, lights, jitter;
     DevBuf fnode;    // 2^f_log2-ary records of the frustum traversal (empty: it takes wnode's 4-ary ones)
     DevBuf qent, qhdr;  // fnode quantised (build_quant_records): the big-scene kernels' records
@@ -2650,6 +2653,205 @@ extern "C" int rt_hit_record_host(const rt_ray* rays, const rt_triangle* tris, i
             h = hit_record(r, e1, e2, mk(T.n0.x, T.n0.y, T.n0.z), mk(T.n1.x, T.n1.y, T.n1.z), mk(T.n2.x, T.n2.y, T.n2.z), t, u,
                            v, i, -1, -1);
         std::memcpy(&out[i], &h, sizeof(rt_hit));
+    }
+    return RT_OK;
+}
+
+// ---- multi-hit queries (rt_multihit.hpp, multi_hit_kernel) --------------------------------------
+static_assert(sizeof(rt_multi_hit) == 16, "rt_multi_hit is one 16-byte word");
+static_assert(mh_class(RT_MULTI_HIT_MAX_K) == RT_MULTI_HIT_MAX_K, "the largest k class is RT_MULTI_HIT_MAX_K");
+
+namespace {
+// As trace_rays_args: no HIP call and no read through s before the checks pass.
+int multi_hits_args(const rt_scene* s, const void* rays, size_t n, int k, int flags, const rt_multi_hit* hits,
+                    const int32_t* count) {
+    if (!s) return set_error(RT_ERR_ARG, "rt_trace_multi_hits: null scene");
+    if (k < 0 || k > RT_MULTI_HIT_MAX_K) return set_error(RT_ERR_ARG, "rt_trace_multi_hits: k outside 0..RT_MULTI_HIT_MAX_K");
+    if (flags & ~RT_FLAG_BINARY) return set_error(RT_ERR_ARG, "rt_trace_multi_hits: unknown flag");
+    if (!rays) return set_error(RT_ERR_ARG, "rt_trace_multi_hits: null rays");
+    if (k > 0 && !hits) return set_error(RT_ERR_ARG, "rt_trace_multi_hits: null hits with k > 0");
+    if (k == 0 && !count) return set_error(RT_ERR_ARG, "rt_trace_multi_hits: k == 0 and a null count: no output");
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_trace_multi_hits: more than 2^31-1 rays in one batch");
+    if ((unsigned long long)n * (unsigned long long)k > 0x7FFFFFFFull)
+        return set_error(RT_ERR_UNSUPPORTED, "rt_trace_multi_hits: more than 2^31-1 records (n * k) in one batch");
+    return RT_OK;
+}
+
+template <int VARIANT>
+void launch_multi_hits(const MultiHitParams& Q, hipStream_t st) {
+    const int kc = mh_class(Q.k);
+    const dim3 block(mh_block(kc)), grid((Q.n + block.x - 1) / block.x);
+    if (kc == 0) hipLaunchKernelGGL((multi_hit_kernel<VARIANT, 0>), grid, block, 0, st, Q);
+    else if (kc == 4) hipLaunchKernelGGL((multi_hit_kernel<VARIANT, 4>), grid, block, 0, st, Q);
+    else if (kc == 8) hipLaunchKernelGGL((multi_hit_kernel<VARIANT, 8>), grid, block, 0, st, Q);
+    else if (kc == 16) hipLaunchKernelGGL((multi_hit_kernel<VARIANT, 16>), grid, block, 0, st, Q);
+    else hipLaunchKernelGGL((multi_hit_kernel<VARIANT, 32>), grid, block, 0, st, Q);
+}
+
+// One launch on st under trace_rays_launch's variant rule; of the scene it writes multi_variant alone.
+int multi_hits_launch(rt_scene* s, const rt_ray* rays, const float* max_t, size_t n, int k, int flags, rt_multi_hit* hits,
+                      int32_t* count, hipStream_t st) {
+    int variant = RT_RAYS_VARIANT_DEEP;
+    if (!s->deep) {
+        if (s->wide && s->lane_wide && !(flags & RT_FLAG_BINARY)) variant = RT_RAYS_VARIANT_WIDE;
+        else if (s->lane_stack) variant = RT_RAYS_VARIANT_BINARY;
+    }
+    if (s->deep && !s->tri.p) return set_error(RT_ERR_INTERNAL, "rt_trace_multi_hits: a deep scene without its triangle array");
+    MultiHitParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.sc = scene_view(s);  // (the packed records; DEEP's completion reads the triangle array)
+    Q.sc.wide = variant == RT_RAYS_VARIANT_WIDE ? 1 : 0;
+    Q.sc.f_log2 = 2;
+    Q.sc.ncut = 0;
+    Q.rays = reinterpret_cast<const float*>(rays);
+    Q.max_t = max_t;
+    Q.n = uint32_t(n);
+    Q.k = k;
+    Q.hits = k > 0 ? reinterpret_cast<uint4*>(hits) : nullptr;
+    Q.count = count;
+    if (variant == RT_RAYS_VARIANT_WIDE) launch_multi_hits<RT_RAYS_VARIANT_WIDE>(Q, st);
+    else if (variant == RT_RAYS_VARIANT_BINARY) launch_multi_hits<RT_RAYS_VARIANT_BINARY>(Q, st);
+    else launch_multi_hits<RT_RAYS_VARIANT_DEEP>(Q, st);
+    HIP_TRY(hipGetLastError());
+    s->multi_variant.store(variant, std::memory_order_relaxed);
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_trace_multi_hits_device(rt_scene* s, const rt_ray* rays, const float* max_t, size_t n, int k, int flags,
+                                          rt_multi_hit* hits, int32_t* count, void* stream) {
+    const int rc = multi_hits_args(s, rays, n, k, flags, hits, count);
+    if (rc != RT_OK) return rc;
+    // the kernel stores 16-byte words
+    if (k > 0 && reinterpret_cast<uintptr_t>(hits) % 16 != 0)
+        return set_error(RT_ERR_ARG, "rt_trace_multi_hits_device: hits_dev is not 16-byte aligned");
+    if (n == 0) return RT_OK;
+    DeviceGuard g(s->device);
+    return multi_hits_launch(s, rays, max_t, n, k, flags, hits, count, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rt_trace_multi_hits(rt_scene* s, const rt_ray* rays, const float* max_t, size_t n, int k, int flags,
+                                   rt_multi_hit* hits, int32_t* count, float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.0f;
+    int rc = multi_hits_args(s, rays, n, k, flags, hits, count);
+    if (rc != RT_OK || n == 0) return rc;
+    DeviceGuard g(s->device);
+    DevBuf dr, dm, dh, dc;
+    const size_t hit_bytes = n * size_t(k) * sizeof(rt_multi_hit);
+    if ((rc = dr.upload(rays, n * sizeof(rt_ray))) != RT_OK) return rc;
+    if (max_t && (rc = dm.upload(max_t, n * sizeof(float))) != RT_OK) return rc;
+    if (k > 0 && (rc = dh.alloc(hit_bytes)) != RT_OK) return rc;
+    if (count && (rc = dc.alloc(n * sizeof(int32_t))) != RT_OK) return rc;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } ev;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, nullptr));
+    }
+    rc = multi_hits_launch(s, static_cast<const rt_ray*>(dr.p), static_cast<const float*>(dm.p), n, k, flags,
+                           static_cast<rt_multi_hit*>(dh.p), static_cast<int32_t*>(dc.p), nullptr);
+    if (rc != RT_OK) return rc;
+    if (kernel_ms) HIP_TRY(hipEventRecord(ev.b, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    if (k > 0) HIP_TRY(hipMemcpy(hits, dh.p, hit_bytes, hipMemcpyDeviceToHost));
+    if (count) HIP_TRY(hipMemcpy(count, dc.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_trace_multi_hits_variant(const rt_scene* s) {
+    return s ? s->multi_variant.load(std::memory_order_relaxed) : RT_RAYS_VARIANT_NONE;
+}
+
+// The host build of the query on arrays in the reference layout: SearchBVH's control flow with the
+// bound fixed at tmax (512-entry stack, overflow flag, brute-force completion), through box_hit and
+// mt_g, the functions the kernel runs; the list is a sort of everything collected.
+extern "C" int rt_multi_hits_host(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                                  const rt_ray* rays, const float* max_t, size_t n, int k, rt_multi_hit* hits,
+                                  int32_t* count) {
+    if (k < 0 || k > RT_MULTI_HIT_MAX_K) return set_error(RT_ERR_ARG, "rt_multi_hits_host: k outside 0..RT_MULTI_HIT_MAX_K");
+    if (P == 0 || P > 0x7FFFFFFFull || !nodes || !aabbs || !tris) return set_error(RT_ERR_ARG, "rt_multi_hits_host: null or empty scene arrays");
+    if (n > 0 && !rays) return set_error(RT_ERR_ARG, "rt_multi_hits_host: null rays");
+    if (k > 0 && !hits) return set_error(RT_ERR_ARG, "rt_multi_hits_host: null hits with k > 0");
+    if (k == 0 && !count) return set_error(RT_ERR_ARG, "rt_multi_hits_host: k == 0 and a null count: no output");
+    if (n > 0x7FFFFFFFull || (unsigned long long)n * (unsigned long long)k > 0x7FFFFFFFull)
+        return set_error(RT_ERR_UNSUPPORTED, "rt_multi_hits_host: more than 2^31-1 rays or records");
+    const size_t nn = 2 * P - 1;
+    // make_ray's bound of |coordinate| over every box (inf when a box is not finite: every test of
+    // every ray is then decided in double)
+    float bm[3] = {0.f, 0.f, 0.f};
+    for (size_t i = 0; i < nn; ++i) {
+        const float c[6] = {aabbs[i].min_corner.x, aabbs[i].min_corner.y, aabbs[i].min_corner.z,
+                            aabbs[i].max_corner.x, aabbs[i].max_corner.y, aabbs[i].max_corner.z};
+        for (int a = 0; a < 6; ++a) bm[a % 3] = std::isfinite(c[a]) ? fmaxf(bm[a % 3], fabsf(c[a])) : INFINITY;
+    }
+    for (size_t i = 0; i < nn; ++i) {
+        if (nodes[i].object_idx != NO_REF) continue;
+        if ((nodes[i].left_idx != NO_REF && nodes[i].left_idx >= nn) || (nodes[i].right_idx != NO_REF && nodes[i].right_idx >= nn))
+            return set_error(RT_ERR_ARG, "rt_multi_hits_host: a child index outside the node array");
+    }
+    auto box_of = [&](uint32_t i) {
+        const rt_aabb& b = aabbs[i];
+        return BoxP{(v2f){b.min_corner.x, b.max_corner.x}, (v2f){b.min_corner.y, b.max_corner.y},
+                    (v2f){b.min_corner.z, b.max_corner.z}};
+    };
+    struct Found {
+        uint32_t tb;  // t's bits: the order of the floats for the t >= 1e-4 that are accepted
+        int32_t tri;
+        float u, v;
+    };
+    std::vector<Found> found;
+    std::vector<uint32_t> stack(REF_STACK);
+    for (size_t i = 0; i < n; ++i) {
+        const rt_ray& q = rays[i];
+        const RayPre r = make_ray(mk(q.origin.x, q.origin.y, q.origin.z), mk(q.direction.x, q.direction.y, q.direction.z),
+                                  mk(bm[0], bm[1], bm[2]));
+        const float tmax = max_t ? max_t[i] : FLT_MAX;
+        auto test = [&](uint32_t tri) {
+            const rt_triangle& T = tris[tri];
+            const f3 v0 = mk(T.v0.x, T.v0.y, T.v0.z);
+            const f3 e1 = sub(mk(T.v1.x, T.v1.y, T.v1.z), v0), e2 = sub(mk(T.v2.x, T.v2.y, T.v2.z), v0);
+            float t, u, v;
+            if (mt_g(r, v0, e1, e2, kRayTMin, tmax, t, u, v)) found.push_back(Found{pw::asu(t), (int32_t)tri, u, v});
+        };
+        found.clear();
+        int sp = 0;
+        bool overflow = false;
+        size_t pops = 0;
+        stack[sp++] = 0;
+        while (sp > 0) {
+            const uint32_t ni = stack[--sp];
+            if (++pops > nn) return set_error(RT_ERR_ARG, "rt_multi_hits_host: the nodes are not a tree");
+            if (!box_hit(r, box_of(ni), kRayTMin, tmax)) continue;
+            const rt_bvh_node& nd = nodes[ni];
+            if (nd.object_idx != NO_REF) {
+                if (nd.object_idx < P) test(nd.object_idx);
+                continue;
+            }
+            for (const uint32_t ch : {nd.left_idx, nd.right_idx}) {
+                if (ch == NO_REF || !box_hit(r, box_of(ch), kRayTMin, tmax)) continue;
+                if (sp < REF_STACK) stack[sp++] = ch;
+                else overflow = true;
+            }
+        }
+        if (overflow) {
+            found.clear();
+            for (size_t t = 0; t < P; ++t) test((uint32_t)t);
+        }
+        std::sort(found.begin(), found.end(),
+                  [](const Found& a, const Found& b) { return a.tb != b.tb ? a.tb < b.tb : a.tri < b.tri; });
+        if (count) count[i] = (int32_t)found.size();
+        for (int j = 0; j < k; ++j) {
+            rt_multi_hit h = {-1, -1.0f, 0.0f, 0.0f};
+            if ((size_t)j < found.size()) h = {found[j].tri, pw::asf(found[j].tb), found[j].u, found[j].v};
+            std::memcpy(&hits[i * size_t(k) + j], &h, sizeof(h));
+        }
     }
     return RT_OK;
 }
