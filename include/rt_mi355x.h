@@ -1121,7 +1121,15 @@ int rt_box_test_batch(int device, const float* rays, const float* boxes, const f
  * tile_misses_box_f).  Item i: the pixel rectangle tiles[4i..] = (x0, x1, y0, y1), columns x0..x1
  * and rows y0..y1 inclusive, of cam's image, and the box boxes[6i..] = (min, max).  out[i] = 1
  * when the test says every camera ray of the rectangle, for any jitter with |entry| <= 1,
- * misses the box. */
+ * misses the box.  As in a frame, the test runs only for a camera whose range of |D| is proven
+ * (rt_debug_camera_class 0); for any other camera every out[i] is 0.
+ *
+ * rt_debug_camera_class: what a frame does with this camera and a jitter table whose largest
+ * |entry| is pad (at least 1).  *out = 0: every |pixel00 + px du + py dv - center| over the padded
+ * frame is proven inside [2e-12, 9e18] (the cull and cut run, any kernel); 1: finite rays, some of
+ * which may take Camera::get_ray's 1e-12 fallback (no cull, no cut); 2: a non-finite word, or a
+ * length that may overflow (the lane kernel, no cull). */
+int rt_debug_camera_class(const rt_camera* cam, float pad, int32_t* out);
 int rt_debug_tile_test_host(const rt_camera* cam, const int32_t* tiles, const float* boxes, int n, int32_t* out);
 int rt_debug_tile_test_batch(int device, const rt_camera* cam, const int32_t* tiles, const float* boxes, int n,
                              int32_t* out);

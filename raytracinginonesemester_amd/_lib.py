@@ -295,6 +295,7 @@ SIGNATURES = {
     "rt_powf_batch": (I, [I, P, P, I, P]),
     "rt_box_test_host": (I, [P, P, P, I, P, P, P]),
     "rt_box_test_batch": (I, [I, P, P, P, P, P, I, P]),
+    "rt_debug_camera_class": (I, [P, C.c_float, P]),
     "rt_debug_tile_test_host": (I, [P, P, P, I, P]),
     "rt_debug_tile_test_batch": (I, [I, P, P, P, I, P]),
     "rt_debug_family_test_host": (I, [P, P, P, P, P, I, P, P]),

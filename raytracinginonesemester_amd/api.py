@@ -78,6 +78,26 @@ class Camera:
         return Camera(self.pos, self.look_at, self.up, self.focal_length_mm, self.sensor_height_mm,
                       width, height)
 
+    @classmethod
+    def from_basis(cls, center, pixel00_loc, pixel_delta_u, pixel_delta_v, width: int, height: int) -> "Camera":
+        """A camera from its four basis vectors as given (any float32 words; no rt_camera_init):
+        what rt_camera holds.  It has no constructor parameters, so no resized()."""
+        self = cls.__new__(cls)
+        self.pos = self.look_at = self.up = self.focal_length_mm = self.sensor_height_mm = None
+        self.c = L.CameraT()
+        self.c.center, self.c.pixel00_loc = _v3(center), _v3(pixel00_loc)
+        self.c.pixel_delta_u, self.c.pixel_delta_v = _v3(pixel_delta_u), _v3(pixel_delta_v)
+        self.c.pixel_width, self.c.pixel_height = int(width), int(height)
+        return self
+
+    def frame_class(self, pad: float = 1.0) -> int:
+        """What a frame does with this camera (rt_debug_camera_class): 0 its |D| range is proven,
+        the cull and cut run; 1 finite rays that may take get_ray's 1e-12 fallback, no cull; 2 a
+        non-finite word or a length that may overflow, the lane kernel without the cull."""
+        out = C.c_int32(-1)
+        check(lib().rt_debug_camera_class(C.byref(self.c), float(pad), C.byref(out)))
+        return int(out.value)
+
 
 def jittered_samples(spp: int, seed: int = 42, centered: bool = True) -> np.ndarray:
     """(spp, 2) float32 sub-pixel offsets (G/include/antialias.h:12-27; HW1 when not centered)."""

@@ -1682,6 +1682,12 @@ bool jitter_finite(const std::vector<float>& tab) {
         if (!std::isfinite(j)) return false;
     return true;
 }
+// The largest |entry| of a finite table: how far a sample may sit from its pixel (camera_class).
+double jitter_pad(const std::vector<float>& tab) {
+    double m = 0.0;
+    for (const float j : tab) m = std::max(m, double(fabsf(j)));
+    return m;
+}
 
 // The render kernel's persistent grid: the blocks of it one dispatch keeps resident on every CU
 // (the occupancy the kernel was compiled for, LDS permitting), a multiple of 8 (one share per
@@ -1861,6 +1867,90 @@ double root_box_coverage(const float* rb, const rt_camera* cam) {
     const double w = std::max(0.0, std::min(W, x1) - std::max(0.0, x0)), h = std::max(0.0, std::min(H, y1) - std::max(0.0, y0));
     return w * h / (W * H);
 }
+
+// What the frame path may assume of a camera.  Camera::get_ray's direction is
+// cam_unit(D) with D(px, py) = (pixel00 + du*px) + dv*py - center in float: D / |D| only while
+// 1e-12 <= |D| (below: the fallback (0,0,1), whatever D is) and |D|^2 stays finite (above ~1.8e19:
+// a zero direction, or NaN once D itself is inf - inf).  The tile tests reason about D, the wave
+// kernels' group-wide tests drop NaN lanes, so render_frame asks here first:
+//   RT_CAMERA_PROVEN  every |D| over the padded frame lies in [2e-12, 9e18]: cull, cut, any kernel;
+//   RT_CAMERA_NO_CULL finite rays, but some may take the fallback: any kernel, no cull and no cut;
+//   RT_CAMERA_LANE    a non-finite word, or a |D| (or a term of it) that may overflow: the lane
+//                     kernel without the cull, the reference's DFS ray by ray.
+// The proof, in double: px in [-pad, W-1+pad], py in [-pad, H-1+pad] (pad: the jitter table's
+// largest |entry|, at least the tile tests' one pixel).  Exact D is affine in (px, py), so |D|
+// is largest at a corner; its smallest value is at least the smaller of the distance from the
+// origin to the plane of the parallelogram and to its four edges, and at least the gap any axis
+// keeps from zero over the four corners.  The float D is within E_a = 6 * 2^-24 * S_a of the exact
+// one on axis a, S_a = |center_a| + |pixel00_a| + pxm |du_a| + pym |dv_a|: the six roundings
+// (px, du*px, the sum, dv*py, the sum, the difference) add up to (3|p00| + 5|du px| + 4|dv py| +
+// |c|) 2^-24.  Margin: a factor 2 on both ends (2e-12, 9e18), far above the 3 roundings of
+// sqrtf(x*x + y*y + z*z) and of this function's own doubles (1e-16), and free: no camera that
+// renders anything lives within a factor 2 of either end.
+constexpr int RT_CAMERA_PROVEN = 0, RT_CAMERA_NO_CULL = 1, RT_CAMERA_LANE = 2;
+int camera_class(const rt_camera* cam, double pad) {
+    const double c[3] = {cam->center.x, cam->center.y, cam->center.z};
+    const double p0[3] = {cam->pixel00_loc.x, cam->pixel00_loc.y, cam->pixel00_loc.z};
+    const double du[3] = {cam->pixel_delta_u.x, cam->pixel_delta_u.y, cam->pixel_delta_u.z};
+    const double dv[3] = {cam->pixel_delta_v.x, cam->pixel_delta_v.y, cam->pixel_delta_v.z};
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(c[a]) || !std::isfinite(p0[a]) || !std::isfinite(du[a]) || !std::isfinite(dv[a]))
+            return RT_CAMERA_LANE;
+    if (!(pad >= 1.0)) pad = 1.0;
+    if (!(pad < 1e30)) return RT_CAMERA_LANE;
+    const double xl = -pad, xh = double(cam->pixel_width) - 1.0 + pad, yl = -pad, yh = double(cam->pixel_height) - 1.0 + pad;
+    const double pxm = std::max(std::fabs(xl), std::fabs(xh)), pym = std::max(std::fabs(yl), std::fabs(yh));
+    constexpr double kU = 6.0 * 5.9604644775390625e-8;
+    double E[3], E2 = 0.0, smax = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        const double S = std::fabs(c[a]) + std::fabs(p0[a]) + pxm * std::fabs(du[a]) + pym * std::fabs(dv[a]);
+        smax = std::max(smax, S);
+        E[a] = kU * S;
+        E2 += E[a] * E[a];
+    }
+    E2 = std::sqrt(E2);
+    if (!(smax < 1e38)) return RT_CAMERA_LANE;  // a term of the float sum may overflow
+    // the corners: the largest |D|, and per axis the range of D
+    double K[4][3], far = 0.0, lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int k = 0; k < 4; ++k) {
+        const double px = (k & 1) ? xh : xl, py = (k & 2) ? yh : yl;
+        double n2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            K[k][a] = (p0[a] - c[a]) + px * du[a] + py * dv[a];
+            n2 += K[k][a] * K[k][a];
+            lo[a] = std::min(lo[a], K[k][a]);
+            hi[a] = std::max(hi[a], K[k][a]);
+        }
+        far = std::max(far, std::sqrt(n2));
+    }
+    if (!(far + E2 <= 9e18)) return RT_CAMERA_LANE;
+    // the smallest |D|: an axis that keeps its sign ...
+    double near_ = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        const double gap = lo[a] > 0.0 ? lo[a] : hi[a] < 0.0 ? -hi[a] : 0.0;
+        near_ = std::max(near_, gap - E[a]);
+    }
+    // ... or the distance to the parallelogram: its plane (0 when the basis is collapsed) and its edges
+    auto dot3 = [](const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
+    const double eu[3] = {K[1][0] - K[0][0], K[1][1] - K[0][1], K[1][2] - K[0][2]};
+    const double ev[3] = {K[2][0] - K[0][0], K[2][1] - K[0][1], K[2][2] - K[0][2]};
+    const double nrm[3] = {eu[1] * ev[2] - eu[2] * ev[1], eu[2] * ev[0] - eu[0] * ev[2], eu[0] * ev[1] - eu[1] * ev[0]};
+    const double nn = std::sqrt(dot3(nrm, nrm));
+    // (a normal lost in the rounding of the cross product proves nothing)
+    double dist = nn > 1e-9 * std::sqrt(dot3(eu, eu) * dot3(ev, ev)) ? std::fabs(dot3(K[0], nrm)) / nn : 0.0;
+    static const int kEdge[4][2] = {{0, 1}, {2, 3}, {0, 2}, {1, 3}};
+    for (const auto& e : kEdge) {
+        const double* A = K[e[0]];
+        const double* B = K[e[1]];
+        const double ab[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+        const double l2 = dot3(ab, ab);
+        const double t = l2 > 0.0 ? std::clamp(-dot3(A, ab) / l2, 0.0, 1.0) : 0.0;
+        const double q[3] = {A[0] + t * ab[0], A[1] + t * ab[1], A[2] + t * ab[2]};
+        dist = std::min(dist, std::sqrt(dot3(q, q)));
+    }
+    near_ = std::max(near_, dist - E2);
+    return near_ >= 2e-12 ? RT_CAMERA_PROVEN : RT_CAMERA_NO_CULL;
+}
 }  // namespace
 
 // Set by rt_count_rays around its one render (the calling thread's frame only).
@@ -1998,7 +2088,11 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     // NaN, and the ray ends on the last triangle of its own DFS.  The lane kernel is that DFS ray by
     // ray; the wave kernels' group-wide tests (the family's min / max drop a NaN lane) are not, so
     // such a frame takes the lane kernel.
-    const int kernel = jitter_finite(s->jitter_host) ? o->kernel : RT_KERNEL_LANE;
+    // A non-finite camera word gives exactly these rays for every sample, and so does a |D| that
+    // overflows (a zero direction, or NaN once the pixel position is inf - inf): camera_class.
+    const bool jfinite = jitter_finite(s->jitter_host);
+    const int cam_class = jfinite ? camera_class(cam, jitter_pad(s->jitter_host)) : RT_CAMERA_LANE;
+    const int kernel = cam_class != RT_CAMERA_LANE ? o->kernel : RT_KERNEL_LANE;
     const bool samples = kernel != RT_KERNEL_WAVE_PIXELS && o->spp <= BLOCK && (o->spp & (o->spp - 1)) == 0;
     // Half waves (32 samples per wave) for the shards of an 8-way split: a shard's kernel is then
     // bound by its longest waves, and halving their rays shortens them (c3 band shards on one
@@ -2040,6 +2134,9 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     // entry is finite with |entry| <= 1, the default table among them.  Any other caller table
     // (a wide reconstruction filter, a sub-frame shift) renders without the cull: as exact.
     if (P.cull && !jitter_within_pad(s->jitter_host)) P.cull = 0;
+    // The tile tests take every ray direction for a positive multiple of D (tile_dirs_f): only a
+    // camera whose |D| range is proven (camera_class) is culled or cut.
+    if (cam_class != RT_CAMERA_PROVEN) P.cull = 0;
     if (!P.cull) P.sc.ncut = 0;  // the render kernel reads the cut pass's lists only when it ran
     P.miss_pixel = miss_pixel_value(o);
     P.nqueues = P.tile_order == RT_TILES_LINEAR ? 1 : 8;
@@ -2082,7 +2179,8 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
                           A.spp == P.spp && A.half_waves == P.half_waves && A.sc.ncut == P.sc.ncut && A.cull == P.cull &&
                           A.heavy_cap == P.heavy_cap && A.queue_cap == P.queue_cap && A.nqueues == P.nqueues &&
                           A.max_depth == P.max_depth && A.paired_only == P.paired_only && A.band_index == P.band_index &&
-                          A.band_count == P.band_count && ps->stream == static_cast<hipStream_t>(stream);
+                          A.band_count == P.band_count && ps->stream == static_cast<hipStream_t>(stream) &&
+                          mode == RT_KERNEL_WAVE;  // (a camera that takes frame B to the lane kernel: camera_class)
         if (!same) {
             pair_b = false;
             if ((rc = flush_pair_a(s, *ps)) != RT_OK) return rc;
@@ -3486,10 +3584,18 @@ extern "C" int rt_debug_tile_test_host(const rt_camera* cam, const int32_t* tile
     RenderParams P;
     std::memset(&P, 0, sizeof(P));
     tile_test_camera(P, *cam);
+    // as in a frame: the tile test runs only for a camera whose |D| range is proven (camera_class)
+    const bool proven = camera_class(cam, 1.0) == RT_CAMERA_PROVEN;
     for (int i = 0; i < n; ++i) {
         const int32_t* t = tiles + 4 * size_t(i);
-        out[i] = tile_misses_box_f(tile_dirs_f(P, t[0], t[1], t[2], t[3]), boxes + 6 * size_t(i)) ? 1 : 0;
+        out[i] = proven && tile_misses_box_f(tile_dirs_f(P, t[0], t[1], t[2], t[3]), boxes + 6 * size_t(i)) ? 1 : 0;
     }
+    return RT_OK;
+}
+
+extern "C" int rt_debug_camera_class(const rt_camera* cam, float pad, int32_t* out) {
+    if (!cam || !out) return set_error(RT_ERR_ARG, "rt_debug_camera_class: null argument");
+    *out = camera_class(cam, double(pad));
     return RT_OK;
 }
 
@@ -3499,6 +3605,10 @@ extern "C" int rt_debug_tile_test_batch(int device, const rt_camera* cam, const 
     int rc = check_device(device);
     if (rc != RT_OK) return rc;
     if (n == 0) return RT_OK;
+    if (camera_class(cam, 1.0) != RT_CAMERA_PROVEN) {  // as in a frame: no tile test, nothing culled
+        std::fill(out, out + n, 0);
+        return RT_OK;
+    }
     DeviceGuard g(device);
     DevBuf dt, db, dout;
     if ((rc = dt.upload(tiles, size_t(n) * 4 * sizeof(int32_t))) != RT_OK) return rc;

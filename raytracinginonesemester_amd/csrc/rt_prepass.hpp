@@ -11,7 +11,12 @@
 // set of nodes holding every leaf exactly once: the root alone, or the cut the scene keeps in
 // sc.cut).  SearchBVH only tests a triangle after its ancestors' box tests passed, with tmax =
 // bestT <= FLT_MAX (a smaller tmax only fails more), so such a ray tests no triangle: a miss.
-// Ray directions are positive multiples of D(px,py) = pixel00 + px*du + py*dv - center with
+// Precondition, checked by the host once per frame (camera_class, rt_device.hip):
+// every |D| over the padded frame is proven inside [2e-12, 9e18], a factor 2 inside the range
+// [1e-12, ~1.8e19] where Camera::get_ray's cam_unit neither falls back to (0,0,1) nor overflows
+// (the factor covers the roundings of the float |D| many times over and excludes no camera that
+// renders anything).  Only then are the
+// ray directions positive multiples of D(px,py) = pixel00 + px*du + py*dv - center with
 // px in [x0-0.5, x1+0.5) for the default jitter table, an affine map: its per-component range
 // over the 1-pixel-padded tile comes from the corners, widened by 1.1e-5*|D| plus 16 float ulps
 // of every term: 8 cover the float rounding of the per-sample computation (pixel position,

@@ -313,3 +313,136 @@ def check_short_batches(fn, name="free"):
     for n in (1, 3, 5, 63, 65):
         o, l = fn(c["rays"], c["active"], c["best_t"], c["bmax"], c["boxes"], n)
         assert np.array_equal(o, out[:n]) and np.array_equal(l, loose[:n]), n
+
+
+# ---- waves of degenerate cameras (tests/camera_cases.py): sound side only --------------------
+# What a frame of a camera outside 1e-12 <= |D| <= ~1.8e19 can bring to a wave: lanes that hold
+# get_ray's fallback (0, 0, 1) beside ordinary directions, lanes with a zero direction (|D|^2
+# overflowed), and 64 identical lanes (intervals of zero width).  NaN lanes are outside the
+# family's contract: its min / max drop them, and render_frame sends such a frame to the lane
+# kernel (camera_class).  A zero direction is parallel on every axis, so the lane's own test is the
+# inside test of the origin on all three.
+DEGENERATE_CASES = ("mixed_fallback", "zero_lanes", "identical")
+
+
+def _degenerate_waves(rng, name):
+    import camera_cases as cc
+
+    def quads(c, spp_of_quad):
+        w, h, spp = spp_of_quad
+        tab = c["table"] if c["spp"] == spp else rt.jittered_samples(spp)
+        rays, _ = rt.camera_rays(c["cam"], spp=spp, jitter=tab)
+        rays = rays.reshape(c["H"], c["W"], spp, 6)
+        for y0 in range(0, c["H"] - h + 1, h):
+            for x0 in range(0, c["W"] - w + 1, w):
+                yield rays[y0:y0 + h, x0:x0 + w].reshape(64, 6).copy()
+
+    fb = np.array([0.0, 0.0, 1.0], F32)
+    if name == "mixed_fallback":
+        # every quad of the threshold and plane frames that holds both kinds, then ordinary
+        # camera quads with lanes overwritten by the fallback
+        for cname in cc.names_of("threshold") + cc.names_of("plane"):
+            for q in QUADS:
+                for r in quads(cc.case(cname), q):
+                    f = cc.is_fallback(r[:, 3:])
+                    if f.any() and not f.all():
+                        yield r, 1.0
+        for k, (r, sc) in enumerate(_camera_waves(rng, "free")):
+            if k % 7 == 0:
+                r[rng.random(64) < float(rng.choice([0.02, 0.5, 0.98])), 3:] = fb
+                yield r, sc
+    elif name == "zero_lanes":
+        for cname in ("ov_partial_du", "ov_partial_du_1e28", "ov_sphere_partial_dv", "ov_sensor_1e25"):
+            for r in quads(cc.case(cname), QUADS[1]):
+                yield r, 1.0
+        for k, (r, sc) in enumerate(_camera_waves(rng, "inside")):
+            if k % 7 == 0:
+                r[rng.random(64) < float(rng.choice([0.02, 0.5, 1.0])), 3:] = rng.choice(np.array([0.0, -0.0], F32))
+                yield r, sc
+    else:
+        for cname in cc.names_of("fallback") + ("co_du0_dv0", "co_up_zero", "ov_pos_1e20"):
+            c = cc.case(cname)
+            for q in QUADS[1:]:
+                for i, r in enumerate(quads(c, q)):
+                    if i % 5 == 0:
+                        yield r, 1.0
+        for k, (r, sc) in enumerate(_camera_waves(rng, "axis")):
+            if k % 7 == 0:
+                r[:, 3:] = r[int(rng.integers(0, 64)), 3:]
+                yield r, sc
+
+
+def _build_degenerate(rng, waves):
+    import camera_cases as cc
+
+    scene_boxes = np.concatenate([np.asarray(cc.scene(s)["aabbs"], F32).reshape(-1, 6)[:15]
+                                  for s in ("above_origin", "sphere_single", "cornell")])
+    R, A, T, M, B = [], [], [], [], []
+    for w, (rays, sc) in enumerate(waves):
+        live = np.ones(64, np.uint8)
+        if w % 3 == 1:
+            live[rng.permutation(64)[:32]] = 0
+        nonzero = (rays[:, 3:] != 0).any(axis=1)
+        aim = (live != 0) & nonzero
+        if not aim.any():  # only zero directions: boxes around the origin and the scenes' own
+            boxes = np.tile(scene_boxes[rng.integers(0, scene_boxes.shape[0], size=32)], (1, 1)).astype(F32)
+            o = rays[0, :3]
+            h = (np.abs(rng.normal(size=(8, 3))) * sc + 0.01 * sc).astype(F32)
+            off = (h * rng.choice([0.0, 0.5, 1.0, 1.5], size=(8, 3)) * rng.choice([-1.0, 1.0], size=(8, 3))).astype(F32)
+            boxes[:8, :3], boxes[:8, 3:] = o + off - h, o + off + h
+        else:
+            boxes, _bd, _sd, _aim = _wave_boxes(rng, rays, aim, sc)
+            boxes = boxes.copy()
+            boxes[24:] = scene_boxes[rng.integers(0, scene_boxes.shape[0], size=8)]
+        mode = w % 4
+        if mode == 0:
+            bt = np.full(64, FLT_MAX, F32)
+        elif mode == 1:
+            bt = np.full(64, TMIN, F32)
+        else:
+            bt = np.where(rng.random(64) < 0.5, FLT_MAX, sc * rng.uniform(0.1, 6.0, size=64)).astype(F32)
+        bm = np.maximum(np.abs(boxes).max(axis=0).reshape(2, 3).max(axis=0), np.abs(scene_boxes).max()) * 2.0
+        R.append(rays), A.append(live), T.append(bt), M.append(bm.astype(F32)), B.append(boxes)
+    case = {"rays": np.ascontiguousarray(R, F32), "active": np.ascontiguousarray(A, np.uint8),
+            "best_t": np.ascontiguousarray(T, F32), "bmax": np.ascontiguousarray(M, F32),
+            "boxes": np.ascontiguousarray(B, F32)}
+    assert np.isfinite(case["rays"]).all()
+    case["any_pass"] = any_lane_passes(case["rays"], case["active"], case["best_t"], case["boxes"])
+    for v in case.values():
+        v.setflags(write=False)
+    return case
+
+
+@lru_cache(maxsize=None)
+def degenerate_case(name: str) -> dict:
+    rng = np.random.default_rng([45, DEGENERATE_CASES.index(name)])
+    return _build_degenerate(rng, list(_degenerate_waves(rng, name)))
+
+
+def check_degenerate(fn, name):
+    """Sound side: no entry rejected while some live lane's own test passes it."""
+    c = degenerate_case(name)
+    out, loose = fn(c["rays"], c["active"], c["best_t"], c["bmax"], c["boxes"])
+    assert np.isin(out, (0, 1)).all()
+    live = c["active"] != 0
+    d = c["rays"][..., 3:]
+    import camera_cases as cc
+
+    fb = cc.is_fallback(d.reshape(-1, 3)).reshape(live.shape) & live
+    zero = (d == 0).all(axis=2) & live
+    same = np.array([(np.unique(d[w][live[w]].view(np.uint32), axis=0).shape[0] == 1) for w in range(d.shape[0])])
+    print(f"{name}: {out.shape[0]} waves (with fallback lanes {int(fb.any(axis=1).sum())}, mixed "
+          f"{int((fb.any(axis=1) & ~(fb | ~live).all(axis=1)).sum())}, with zero lanes {int(zero.any(axis=1).sum())}, "
+          f"identical {int(same.sum())}), loose {float(loose.mean()):.3f}, some lane passes {float(c['any_pass'].mean()):.3f}, "
+          f"rejected of the rest {float((out[~c['any_pass']] == 0).mean()):.3f}")
+    assert out.shape[0] >= 40 and c["any_pass"].any() and (~c["any_pass"]).any()
+    if name == "mixed_fallback":
+        assert (fb.any(axis=1) & ~(fb | ~live).all(axis=1)).sum() >= 20
+    elif name == "zero_lanes":
+        assert zero.any(axis=1).sum() >= 20 and (zero | ~live).all(axis=1).any()
+    else:
+        assert same.sum() >= 20
+    bad = np.argwhere(c["any_pass"] & (out == 0))
+    assert bad.shape[0] == 0, (f"{name}: {bad.shape[0]} of {out.size} entries rejected although a live lane's own "
+                               f"test passes\n" + describe(c, bad))
+    return out, loose

@@ -10,6 +10,7 @@ reference's own code: jitter tables, ray-triangle KAT answers, camera bases, sce
     python tests/golden/gen_golden.py --only c3_small
     python tests/golden/gen_golden.py --only 'shade_*'
     python tests/golden/gen_golden.py --only 'ties_*'
+    python tests/golden/gen_golden.py --only cameras
 """
 from __future__ import annotations
 
@@ -253,6 +254,51 @@ def gen_ties(name: str) -> None:
         (dst / "meta.json").write_text(json.dumps(meta, indent=1) + "\n")
 
 
+CAMERA_FRAME = (16, 8, 4)  # W, H, spp of the camera fixtures; depth 1 and 2 each
+
+
+def gen_cameras() -> None:
+    """Degenerate, extreme and non-finite cameras (tests/camera_cases.py: every case given by the
+    five constructor parameters) on the above_origin scene through the reference's Camera, render()
+    and SearchBVH (ref_g arrays; camera.txt's %a takes nan and inf).  One file per kind of output,
+    the cases' arrays one after the other in meta.json's order."""
+    sys.path.insert(0, str(HERE.parent))
+    import camera_cases
+
+    W, H, spp = CAMERA_FRAME
+    s = camera_cases.scene("above_origin")
+    dst = HERE / "cameras"
+    dst.mkdir(parents=True, exist_ok=True)
+    cases = []
+    with tempfile.TemporaryDirectory() as td:
+        t = Path(td)
+        for k, nm in (("nodes", "nodes.bin"), ("aabbs", "aabbs.bin"), ("tris", "tris.bin"), ("objids", "triobj.bin"),
+                      ("mats", "mats.bin"), ("lights", "lights.bin")):
+            s[k].tofile(t / nm)
+        outs = {k: open(t / ("all_" + k), "wb") for k in ("fb.f32", "hits.i32", "hitt.f32")}
+        for name in camera_cases.CTOR_NAMES:
+            if camera_cases.TABLE[name][1] != "above_origin":
+                continue
+            pos, look, up, focal, sensor = camera_cases.TABLE[name][2][1]
+            (t / "camera.txt").write_text(" ".join(float(v).hex() for v in (*pos, *look, *up, focal, sensor)) + "\n")
+            for depth in (1, 2):
+                run([REF / "ref_g", "arrays", t, t, W, H, spp, depth, 1])
+                meta = json.loads((t / "meta.json").read_text())
+                cases.append({"name": name, "depth": depth, "camera": [float(v).hex() for v in (*pos, *look, *up, focal, sensor)],
+                              **{k: meta[k] for k in ("center", "pixel00_loc", "pixel_delta_u", "pixel_delta_v")}})
+                for k, f in outs.items():
+                    f.write((t / k).read_bytes())
+        for k, f in outs.items():
+            f.close()
+            gz(t / ("all_" + k), dst / (k + ".gz"))
+    doc = {"generator": "tests/camera_cases.py CTOR_NAMES on scene('above_origin')", "width": W, "height": H, "spp": spp,
+           "sha256": {k: hashlib.sha256(s[k].tobytes()).hexdigest() for k in ("nodes", "aabbs", "tris", "objids", "mats", "lights")},
+           "cases": []}
+    # one line per case
+    text = json.dumps(doc, indent=1).replace('"cases": []', '"cases": [\n  ' + ",\n  ".join(json.dumps(c) for c in cases) + "\n ]")
+    (dst / "meta.json").write_text(text + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*")
@@ -274,6 +320,8 @@ def main() -> None:
     for full, n in ties_cases().items():
         if not want or any(fnmatch.fnmatchcase(full, w) for w in want):
             gen_ties(n)
+    if not want or "cameras" in want:
+        gen_cameras()
     if not want or "jitter" in want:
         gen_jitter()
     if not want or "kat" in want:

@@ -396,3 +396,75 @@ def check_short_batches(fn, name="axis"):
         full = fn(g["cam"], tiles, boxes)
         for n in (1, 63, 65):
             assert np.array_equal(fn(g["cam"], tiles, boxes, n), full[:n]), n
+
+
+# ---- degenerate cameras (tests/camera_cases.py): sound side only -----------------------------
+# The tile test takes every ray direction for a positive multiple of D = pixel00 + px du + py dv
+# - center; get_ray's direction is that only while 1e-12 <= |D| <= ~1.8e19.
+# These sets hold the test, as a frame runs it (behind the camera's class), against the rays of
+# cameras outside that range.  No tight side: such a camera is not culled at all.
+CAMERA_TILE_CASES = ("fallback", "threshold", "overflow", "nonfinite")
+
+
+def _camera_boxes(rng, c, n_random=24):
+    """The scene's root and the boxes of its first tree levels (what a cut is made of), then boxes
+    on all sides of the camera: at distances 0.5 to 4 along the six axes and along random
+    directions, sized 0.05 to 1."""
+    import camera_cases as cc
+
+    aabbs = np.asarray(cc.scene(c["scene"])["aabbs"], F32).reshape(-1, 6)
+    boxes = [aabbs[:31]]
+    ctr = c["cam"].basis()["center"].astype(np.float64)
+    ctr = np.where(np.isfinite(ctr) & (np.abs(ctr) < 1e6), ctr, 0.0)
+    dirs = np.concatenate([np.eye(3), -np.eye(3), rng.normal(size=(n_random - 6, 3))])
+    dirs /= np.linalg.norm(dirs, axis=1)[:, None]
+    q = ctr + dirs * rng.choice([0.5, 1.0, 2.0, 4.0], size=(n_random, 1))
+    h = rng.choice([0.05, 0.3, 1.0], size=(n_random, 1)) * rng.uniform(0.5, 1.0, size=(n_random, 3))
+    boxes.append(np.concatenate([q - h, q + h], axis=1).astype(F32))
+    return np.ascontiguousarray(np.concatenate(boxes), F32)
+
+
+@lru_cache(maxsize=None)
+def camera_tile_case(name: str) -> tuple:
+    import camera_cases as cc
+
+    rng = np.random.default_rng([33, CAMERA_TILE_CASES.index(name)])
+    groups = []
+    for cname in cc.names_of(name):
+        c = cc.case(cname)
+        W, H = c["W"], c["H"]
+        rects = {(0, min(7, W - 1), 0, min(7, H - 1)), (max(0, W - 8), W - 1, max(0, H - 8), H - 1),
+                 (W // 2, W // 2, H // 2, H // 2), (0, W - 1, 0, 0)}
+        for rect in sorted(rects):
+            rays = tile_rays(c["cam"], rect)
+            boxes = _camera_boxes(rng, c)
+            tiles = np.ascontiguousarray(np.tile(np.array(rect, np.int32), (boxes.shape[0], 1)))
+            finite = np.isfinite(rays).all(axis=1)
+            # a non-finite ray counts as passing every box: every compare of the reference's is false
+            any_pass = np.ones(boxes.shape[0], bool) if not finite.all() else any_ray_passes(rays, boxes)
+            if not finite.all() and finite.any():
+                any_pass |= any_ray_passes(rays[finite], boxes)
+            g = {"cam": c["cam"], "case": cname, "rect": rect, "tiles": tiles, "boxes": boxes, "any_pass": any_pass}
+            for v in g.values():
+                if isinstance(v, np.ndarray):
+                    v.setflags(write=False)
+            groups.append(g)
+    return tuple(groups)
+
+
+def check_camera_set(fn, name):
+    """Sound side: nothing culled where a ray of the tile passes the box.  Returns the cases with
+    an unsound item (empty when the set passes) after printing the counts."""
+    groups = camera_tile_case(name)
+    got = run_groups(fn, groups)
+    assert np.isin(got, (0, 1)).all()
+    any_pass = gather(groups, "any_pass")
+    bad = any_pass & (got == 1)
+    sizes = np.cumsum([0] + [g["tiles"].shape[0] for g in groups])
+    bad_cases = sorted({g["case"] for i, g in enumerate(groups) if bad[sizes[i]:sizes[i + 1]].any()})
+    print(f"{name}: {got.size} items in {len(groups)} groups, some ray passes {float(any_pass.mean()):.3f}, culled "
+          f"{int(got.sum())}, culled although a ray passes {int(bad.sum())} in cases {bad_cases}")
+    assert any_pass.any()
+    assert not bad.any(), (f"{name}: {int(bad.sum())} of {got.size} items culled although a ray of the tile passes the "
+                           f"box, in cases {bad_cases}\n" + describe(groups, np.flatnonzero(bad)))
+    return got
