@@ -55,7 +55,9 @@ extern "C" {
                                  rt_ray_keys_device, rt_ray_sort_host, rt_ray_sort_scratch_bytes,
                                  rt_ray_sort_device, rt_gather_device, rt_scatter_device; rt_multi_hit,
                                  RT_MULTI_HIT_MAX_K, rt_trace_multi_hits, rt_trace_multi_hits_device,
-                                 rt_trace_multi_hits_variant, rt_multi_hits_host */
+                                 rt_trace_multi_hits_variant, rt_multi_hits_host; rt_point_hit,
+                                 rt_closest_points, rt_closest_points_device,
+                                 rt_closest_points_variant, rt_closest_points_host */
 
 enum {
     RT_OK = 0,
@@ -782,6 +784,80 @@ int rt_trace_multi_hits_variant(const rt_scene* s);
  * RT_ERR_ARG. */
 int rt_multi_hits_host(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
                        const rt_ray* rays, const float* max_t, size_t n, int k, rt_multi_hit* hits, int32_t* count);
+
+/* ---- closest-point queries on a resident scene ------------------------------------------------
+ * The query that starts from a point, not a ray: per point the nearest triangle
+ * of the scene, the squared distance and the nearest point — distance fields, snapping and picking
+ * without a direction, proximity tests, attribute transfer between meshes.
+ *
+ * Definition.  All arithmetic is float32 without contraction; dot(x, y) = (x0*y0 + x1*y1) + x2*y2,
+ * len2(x) = dot(x, x).  The surfaces are the scene's leaves: node j in [P-1, 2P-1) with
+ * object_idx = i < P, its triangle a = v0, e1 = v1 - v0, e2 = v2 - v0 (intersectTriangle's edges),
+ * its box B_j = aabbs[j]; a leaf that names no triangle contributes nothing.  For a point q and a
+ * leaf, with the regions tested in this order and the first match winning:
+ *   ap = q - a;  d1 = dot(e1, ap);  d2 = dot(e2, ap)
+ *   A  (region 0): d1 <= 0 && d2 <= 0                     -> v = 0, w = 0
+ *   bp = ap - e1; d3 = dot(e1, bp);  d4 = dot(e2, bp)
+ *   B  (1): d3 >= 0 && d4 <= d3                            -> v = 1, w = 0
+ *   vc = d1*d4 - d3*d2
+ *   AB (3): vc <= 0 && d1 >= 0 && d3 <= 0                  -> v = d1 / (d1 - d3), w = 0
+ *   cp = ap - e2; d5 = dot(e1, cp);  d6 = dot(e2, cp)
+ *   C  (2): d6 >= 0 && d5 <= d6                            -> v = 0, w = 1
+ *   vb = d5*d2 - d1*d6
+ *   AC (4): vb <= 0 && d2 >= 0 && d6 <= 0                  -> v = 0, w = d2 / (d2 - d6)
+ *   va = d3*d6 - d5*d4
+ *   BC (5): va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0    -> w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w
+ *   face (6): otherwise                                    -> den = 1 / ((va + vb) + vc); v = vb*den; w = vc*den
+ *   p   = (a + e1*v) + e2*w                     per component, for every region
+ *   p_c = p_c < lo_c ? lo_c : (p_c > hi_c ? hi_c : p_c)    confinement to B_j (a NaN stays NaN)
+ *   D   = len2(q - p)
+ * A candidate is accepted iff D < best_D || (D == best_D && i < best_tri), from best_D = max_d2[k]
+ * (+inf when max_d2 is NULL) and best_tri = INT32_MAX: a surface at exactly max_d2 counts, the
+ * lowest triangle index wins ties, a NaN D or a NaN bound never wins.  The answer is that of the
+ * brute force over every leaf; the confinement is what makes the float distance to a box,
+ * lb(q, B) = len2(q - c) with c = q confined to B, a lower bound of every D below it, so that the
+ * kernel's pruned walk (a box is skipped iff lb > best_D) returns the same bytes in any order.
+ * Output per point: the winner's rt_point_hit bit for bit, or {-1, -1.0f, 0, 0, 0, 0, 0, -1}; every
+ * byte is written.  evals (may be NULL): per point the number of leaf triangles whose D was
+ * computed (a lane whose stack filled up restarts with a scan of every leaf and reports their
+ * number): a diagnostic of the pruning.
+ * Specified for finite points and a tree whose boxes contain their children's boxes (rt_build_bvh*,
+ * rt_refit_aabbs_host, refit and rebuild give such trees); for any bit patterns the call
+ * terminates, visits a node at most once and writes every output.
+ * Arguments: RT_ERR_ARG for a null scene, points or hits, a hits_dev that is not 16-byte aligned
+ * (the kernel stores 16-byte words; the host entry's `hits` needs no alignment), a points, max_d2
+ * or evals that is not 4-byte aligned, a flag bit other than RT_FLAG_BINARY; n == 0 is RT_OK with
+ * no launch; n > 2^31-1 is RT_ERR_UNSUPPORTED.  Every argument check runs before any HIP call.
+ * Like the other queries it reads only the scene's current packed arrays and takes no part in the
+ * frame ordering: any stream, any thread, beside frames of the same scene or of a clone.
+ * (Additive to ABI 3: rt_point_hit, rt_closest_points, rt_closest_points_device,
+ * rt_closest_points_variant, rt_closest_points_host.) */
+typedef struct {            /* 32 bytes */
+    int32_t tri;            /* triangle index; -1: no surface within the bound */
+    float   d2;             /* D, the squared distance */
+    float   p[3];           /* the nearest point, confined to its leaf's box */
+    float   v, w;           /* p = a + e1*v + e2*w before the confinement */
+    int32_t region;         /* 0 A, 1 B, 2 C, 3 AB, 4 AC, 5 BC, 6 face; -1: none */
+} rt_point_hit;
+
+/* Asynchronous on hip_stream (NULL = the null stream); device pointers on the scene's device:
+ * points_dev 3n floats, max_d2_dev n floats (or NULL), hits_dev n rt_point_hit (16-byte aligned),
+ * evals_dev n (or NULL). */
+int rt_closest_points_device(rt_scene* s, const float* points_dev, const float* max_d2_dev, size_t n, int flags,
+                             rt_point_hit* hits_dev, uint32_t* evals_dev, void* hip_stream);
+/* Host arrays; uploads, queries, downloads, synchronises.  kernel_ms (may be NULL): HIP-event time
+ * of the kernel. */
+int rt_closest_points(rt_scene* s, const float* points, const float* max_d2, size_t n, int flags,
+                      rt_point_hit* hits, uint32_t* evals, float* kernel_ms);
+/* RT_RAYS_VARIANT_* of the latest rt_closest_points[_device] call on s (NONE before the first), by
+ * rt_trace_rays_variant's rule; a word of its own, which the other queries do not write. */
+int rt_closest_points_variant(const rt_scene* s);
+/* The host build of the query (no device needed) and its definition: the brute force over the
+ * leaves in index order, on arrays in the reference layout (P triangles, 2P-1 nodes and boxes),
+ * through the arithmetic the kernel runs.  evals (may be NULL) gets the number of leaves that name
+ * a triangle. */
+int rt_closest_points_host(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                           const float* points, const float* max_d2, size_t n, rt_point_hit* hits, uint32_t* evals);
 
 /* Camera rays of image rows [row0, row0 + rows): the rays render() shoots and the rng states it
  * gives them (G/include/query.cu:146-158), for rt_trace_rays / rt_trace_hits / rt_shade_rays.  The

@@ -12,6 +12,7 @@ from ._lib import (RTError, RT_DELIVER_DEVICE, RT_DELIVER_F32, RT_DELIVER_NONE, 
                    RT_MULTI_HIT_MAX_K)
 from .api import (  # noqa: F401
     MULTI_HIT_DTYPE, multi_hits_host,
+    POINT_HIT_DTYPE, closest_points_host,
     HIT_DTYPE, LIGHT_DTYPE, AdaptiveFilm, Camera, DeviceScene, Film, HostScene, HW1Scene, MeshHW1, Renderer, build_bvh, comm_unique_id, build_bvh_device, default_material, device_count,
     afilm_host, camera_rays, camera_rays_pixels, film_pixels_host, encode_p6, encode_p6_device, hit_fields, hit_record_host, intersect_rays, jittered_samples, p6_header, quantize_p6_device, read_p6,
     PathState, compact_paths, path_finish, path_step_host, refit_aabbs, triangles_from_mesh, build_bvh_triangles,

@@ -247,6 +247,10 @@ SIGNATURES = {
     "rt_trace_multi_hits": (I, [P, P, P, SZ, I, I, P, P, P]),
     "rt_trace_multi_hits_variant": (I, [P]),
     "rt_multi_hits_host": (I, [SZ, P, P, P, P, P, SZ, I, P, P]),
+    "rt_closest_points_device": (I, [P, P, P, SZ, I, P, P, P]),
+    "rt_closest_points": (I, [P, P, P, SZ, I, P, P, P]),
+    "rt_closest_points_variant": (I, [P]),
+    "rt_closest_points_host": (I, [SZ, P, P, P, P, P, SZ, P, P]),
     "rt_camera_rays_host": (I, [P, I, P, I, I, P, P]),
     "rt_camera_rays_device": (I, [I, P, I, P, I, I, P, P, P]),
     "rt_camera_rays_pass_host": (I, [P, I, I, P, I, I, P, P]),

@@ -37,6 +37,9 @@ assert HIT_DTYPE.itemsize == C.sizeof(L.Hit) == 64
 # rt_multi_hit: one list entry of DeviceScene.trace_multi_hits
 MULTI_HIT_DTYPE = np.dtype([("tri", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4")])
 assert MULTI_HIT_DTYPE.itemsize == 16
+# rt_point_hit: one answer of DeviceScene.closest_points
+POINT_HIT_DTYPE = np.dtype([("tri", "<i4"), ("d2", "<f4"), ("p", "<f4", 3), ("v", "<f4"), ("w", "<f4"), ("region", "<i4")])
+assert POINT_HIT_DTYPE.itemsize == 32
 
 
 def _v3(v) -> L.Vec3:
@@ -870,6 +873,75 @@ class DeviceScene:
         """The traversal the latest trace_multi_hits / count_hits call launched (RT_RAYS_VARIANT_*)."""
         return int(lib().rt_trace_multi_hits_variant(self._handle()))
 
+    def closest_points(self, points, max_d2=None, flags: int = 0, stream: Optional[int] = None, timing: bool = False,
+                       evals: bool = False):
+        """The nearest triangle to each query point (rt_closest_points / rt_closest_points_device,
+        DESIGN.md §4.28): the brute-force minimum of (squared distance, triangle index) over the
+        scene's leaves in the float32 arithmetic of include/rt_mi355x.h, found by a walk that prunes
+        by the distance to a box.  ``points`` (n, 3) float32; ``max_d2`` (n,) float32 bounds on the
+        squared distance (a surface at exactly the bound counts; None: +inf).
+
+        Returns ``(tri, d2, p, v, w, region)``: ``tri`` (n,) int32, ``d2`` (n,) float32, ``p`` (n, 3)
+        float32 the nearest point, ``v``, ``w`` its coordinates along e1 and e2, ``region`` (n,) int32
+        (0 A, 1 B, 2 C, 3 AB, 4 AC, 5 BC, 6 face); -1, -1.0, 0, 0, 0, -1 without a surface in bound.
+        ``evals=True`` appends the number of leaf triangles evaluated per point (n,) uint32 (int32
+        bits on the device path).
+
+        A numpy array takes the host path (upload, query, download, synchronise; ``timing=True``
+        appends the kernel's HIP-event ms).  Torch tensors on the scene's device take the device
+        path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no
+        host synchronisation, tensors returned (views of one (n, 8) record tensor).  ``flags``:
+        RT_FLAG_BINARY or 0."""
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            if points.device != dev or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+                raise ValueError(f"closest_points: expects an (n, 3) float32 tensor on {dev}")
+            if timing:
+                raise ValueError("closest_points: timing is measured on the host path only")
+            points = points.contiguous()
+            n = points.shape[0]
+            md = None
+            if max_d2 is not None:
+                md = torch.as_tensor(max_d2, dtype=torch.float32, device=dev).contiguous()
+                if md.shape != (n,):
+                    raise ValueError("closest_points: max_d2 must hold one float per point")
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            rec = torch.empty((n, 8), dtype=torch.int32, device=dev)
+            ev = torch.empty(n, dtype=torch.int32, device=dev) if evals else None
+            if n > 0:  # (an empty tensor has no address to pass)
+                check(lib().rt_closest_points_device(self._handle(), points.data_ptr(), None if md is None else md.data_ptr(),
+                                                     n, int(flags), rec.data_ptr(), None if ev is None else ev.data_ptr(),
+                                                     stream))
+            _used_on(stream, dev, points, md)
+            f = rec.view(torch.float32)
+            out = (rec[:, 0], f[:, 1], f[:, 2:5], f[:, 5], f[:, 6], rec[:, 7])
+            return (*out, ev) if evals else out
+        q = _c(points, np.float32)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise ValueError("closest_points: expects an (n, 3) array of points")
+        n = q.shape[0]
+        md = None
+        if max_d2 is not None:
+            md = _c(max_d2, np.float32)
+            if md.shape != (n,):
+                raise ValueError("closest_points: max_d2 must hold one float per point")
+        rec = np.zeros(n, POINT_HIT_DTYPE)
+        ev = np.zeros(n, np.uint32) if evals else None
+        ms = C.c_float(0.0)
+        check(lib().rt_closest_points(self._handle(), ptr(q), ptr(md), n, int(flags), ptr(rec), ptr(ev),
+                                      C.byref(ms) if timing else None))
+        out = _point_hit_fields(rec)
+        if evals:
+            out = (*out, ev)
+        return (*out, ms.value) if timing else out
+
+    def closest_points_variant(self) -> int:
+        """The traversal the latest closest_points call launched (RT_RAYS_VARIANT_*)."""
+        return int(lib().rt_closest_points_variant(self._handle()))
+
     # ---- path stages for caller hits (rt_path_*) ------------------------------------------------
     def _torch_dev(self):
         import torch
@@ -1333,6 +1405,37 @@ def multi_hits_host(nodes, aabbs, triangles, rays, k: int, max_t=None):
     check(lib().rt_multi_hits_host(P, ptr(nd), ptr(bx), ptr(tr), ptr(r), ptr(mt), n, k, ptr(rec) if k > 0 else None,
                                    ptr(count)))
     return count, rec["tri"], rec["t"], rec["u"], rec["v"]
+
+
+def _point_hit_fields(rec: np.ndarray):
+    """(tri, d2, p, v, w, region) of a POINT_HIT_DTYPE array, each contiguous."""
+    return tuple(np.ascontiguousarray(rec[f]) for f in ("tri", "d2", "p", "v", "w", "region"))
+
+
+def closest_points_host(nodes, aabbs, triangles, points, max_d2=None, evals: bool = False):
+    """Host build of DeviceScene.closest_points (rt_closest_points_host, no device) and its
+    definition: the brute force over the leaves in index order, on arrays in the reference layout:
+    ``nodes`` (2P-1, 4) uint32, ``aabbs`` (2P-1, 6), ``triangles`` (P, 18), ``points`` (n, 3) float32,
+    ``max_d2`` (n,) float32 or None (+inf).  Returns ``(tri, d2, p, v, w, region)`` as the numpy path
+    of closest_points does; ``evals=True`` appends the number of leaves that name a triangle, per
+    point."""
+    nd, bx, tr, q = _c(nodes, np.uint32), _c(aabbs, np.float32), _c(triangles, np.float32), _c(points, np.float32)
+    P = tr.size // 18
+    if P == 0 or nd.size != 4 * (2 * P - 1) or bx.size != 6 * (2 * P - 1):
+        raise ValueError("closest_points_host: expects 2P-1 nodes and boxes for P >= 1 triangles")
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError("closest_points_host: expects an (n, 3) array of points")
+    n = q.shape[0]
+    md = None
+    if max_d2 is not None:
+        md = _c(max_d2, np.float32)
+        if md.shape != (n,):
+            raise ValueError("closest_points_host: max_d2 must hold one float per point")
+    rec = np.zeros(n, POINT_HIT_DTYPE)
+    ev = np.zeros(n, np.uint32) if evals else None
+    check(lib().rt_closest_points_host(P, ptr(nd), ptr(bx), ptr(tr), ptr(q), ptr(md), n, ptr(rec), ptr(ev)))
+    out = _point_hit_fields(rec)
+    return (*out, ev) if evals else out
 
 
 # rt_hit's 32-bit words by field: (first word, words, float)

@@ -196,6 +196,7 @@ struct RenderParams {
 #include "rt_prepass.hpp"
 #include "rt_query.hpp"
 #include "rt_multihit.hpp"
+#include "rt_closest.hpp"
 #include "rt_path.hpp"
 #include "rt_refit.hpp"
 #include "rt_rebuild.hpp"
@@ -737,6 +738,8 @@ struct rt_scene : rt::SceneMeta {  // the packed scene's facts (rt_scene_pack.hp
     std::atomic<int> path_variant{RT_RAYS_VARIANT_NONE};
     // ... and of the latest rt_trace_multi_hits[_device] call
     std::atomic<int> multi_variant{RT_RAYS_VARIANT_NONE};
+    // ... and of the latest rt_closest_points[_device] call
+    std::atomic<int> closest_variant{RT_RAYS_VARIANT_NONE};
     DevBuf inode, wnode, ibox, leaf, tnorm, objids, mats, lights, jitter;
     DevBuf fnode;    // 2^f_log2-ary records of the frustum traversal (empty: it takes wnode's 4-ary ones)
     DevBuf qent, qhdr;  // fnode quantised (build_quant_records): the big-scene kernels' records
@@ -2950,6 +2953,147 @@ extern "C" int rt_multi_hits_host(size_t P, const rt_bvh_node* nodes, const rt_a
             if ((size_t)j < found.size()) h = {found[j].tri, pw::asf(found[j].tb), found[j].u, found[j].v};
             std::memcpy(&hits[i * size_t(k) + j], &h, sizeof(h));
         }
+    }
+    return RT_OK;
+}
+
+// ---- closest-point queries (rt_closest.hpp, closest_points_kernel) ------------------------------
+static_assert(sizeof(rt_point_hit) == 32, "rt_point_hit is two 16-byte words");
+
+namespace {
+// As multi_hits_args: no HIP call and no read through s before the checks pass.
+int closest_args(const rt_scene* s, const float* points, const float* max_d2, size_t n, int flags, const rt_point_hit* hits,
+                 const uint32_t* evals) {
+    if (!s) return set_error(RT_ERR_ARG, "rt_closest_points: null scene");
+    if (flags & ~RT_FLAG_BINARY) return set_error(RT_ERR_ARG, "rt_closest_points: unknown flag");
+    if (!points) return set_error(RT_ERR_ARG, "rt_closest_points: null points");
+    if (!hits) return set_error(RT_ERR_ARG, "rt_closest_points: null hits");
+    if (reinterpret_cast<uintptr_t>(points) % 4 != 0 || reinterpret_cast<uintptr_t>(max_d2) % 4 != 0 ||
+        reinterpret_cast<uintptr_t>(evals) % 4 != 0)
+        return set_error(RT_ERR_ARG, "rt_closest_points: points, max_d2 or evals is not 4-byte aligned");
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_closest_points: more than 2^31-1 points in one batch");
+    return RT_OK;
+}
+
+// One launch on st under trace_rays_launch's variant rule; of the scene it writes closest_variant alone.
+int closest_launch(rt_scene* s, const float* points, const float* max_d2, size_t n, int flags, rt_point_hit* hits,
+                   uint32_t* evals, hipStream_t st) {
+    int variant = RT_RAYS_VARIANT_DEEP;
+    if (!s->deep) {
+        if (s->wide && s->lane_wide && !(flags & RT_FLAG_BINARY)) variant = RT_RAYS_VARIANT_WIDE;
+        else if (s->lane_stack) variant = RT_RAYS_VARIANT_BINARY;
+    }
+    ClosestParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.sc = scene_view(s);
+    Q.sc.wide = variant == RT_RAYS_VARIANT_WIDE ? 1 : 0;
+    Q.sc.f_log2 = 2;
+    Q.sc.ncut = 0;
+    Q.points = points;
+    Q.max_d2 = max_d2;
+    Q.n = uint32_t(n);
+    // The leaf array keeps one zeroed record when no leaf names a triangle; the root is then a
+    // leaf that names none, which pack_bounds marks with the empty root box.
+    const bool no_leaf = (s->root_ref & LEAF_BIT) && s->root_box[0] > s->root_box[3];
+    Q.n_leaf = no_leaf ? 0u : uint32_t(s->leaf.n / (4 * sizeof(float4)));
+    Q.hits = reinterpret_cast<uint4*>(hits);
+    Q.evals = evals;
+    const dim3 block(BLOCK), grid((Q.n + BLOCK - 1) / BLOCK);
+    if (variant == RT_RAYS_VARIANT_WIDE) hipLaunchKernelGGL(closest_points_kernel<RT_RAYS_VARIANT_WIDE>, grid, block, 0, st, Q);
+    else if (variant == RT_RAYS_VARIANT_BINARY) hipLaunchKernelGGL(closest_points_kernel<RT_RAYS_VARIANT_BINARY>, grid, block, 0, st, Q);
+    else hipLaunchKernelGGL(closest_points_kernel<RT_RAYS_VARIANT_DEEP>, grid, block, 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    s->closest_variant.store(variant, std::memory_order_relaxed);
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_closest_points_device(rt_scene* s, const float* points, const float* max_d2, size_t n, int flags,
+                                        rt_point_hit* hits, uint32_t* evals, void* stream) {
+    const int rc = closest_args(s, points, max_d2, n, flags, hits, evals);
+    if (rc != RT_OK) return rc;
+    // the kernel stores 16-byte words
+    if (reinterpret_cast<uintptr_t>(hits) % 16 != 0)
+        return set_error(RT_ERR_ARG, "rt_closest_points_device: hits_dev is not 16-byte aligned");
+    if (n == 0) return RT_OK;
+    DeviceGuard g(s->device);
+    return closest_launch(s, points, max_d2, n, flags, hits, evals, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rt_closest_points(rt_scene* s, const float* points, const float* max_d2, size_t n, int flags,
+                                 rt_point_hit* hits, uint32_t* evals, float* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0.0f;
+    int rc = closest_args(s, points, max_d2, n, flags, hits, evals);
+    if (rc != RT_OK || n == 0) return rc;
+    DeviceGuard g(s->device);
+    DevBuf dp, dm, dh, de;
+    if ((rc = dp.upload(points, n * 3 * sizeof(float))) != RT_OK) return rc;
+    if (max_d2 && (rc = dm.upload(max_d2, n * sizeof(float))) != RT_OK) return rc;
+    if ((rc = dh.alloc(n * sizeof(rt_point_hit))) != RT_OK) return rc;
+    if (evals && (rc = de.alloc(n * sizeof(uint32_t))) != RT_OK) return rc;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } ev;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, nullptr));
+    }
+    rc = closest_launch(s, static_cast<const float*>(dp.p), static_cast<const float*>(dm.p), n, flags,
+                        static_cast<rt_point_hit*>(dh.p), static_cast<uint32_t*>(de.p), nullptr);
+    if (rc != RT_OK) return rc;
+    if (kernel_ms) HIP_TRY(hipEventRecord(ev.b, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    HIP_TRY(hipMemcpy(hits, dh.p, n * sizeof(rt_point_hit), hipMemcpyDeviceToHost));
+    if (evals) HIP_TRY(hipMemcpy(evals, de.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_closest_points_variant(const rt_scene* s) {
+    return s ? s->closest_variant.load(std::memory_order_relaxed) : RT_RAYS_VARIANT_NONE;
+}
+
+// The host build of the query on arrays in the reference layout, and its definition: every leaf
+// in index order through cp_triangle and cp_wins, the functions the kernel runs.  No tree walk.
+extern "C" int rt_closest_points_host(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
+                                      const float* points, const float* max_d2, size_t n, rt_point_hit* hits,
+                                      uint32_t* evals) {
+    if (P == 0 || P > 0x7FFFFFFFull || !nodes || !aabbs || !tris)
+        return set_error(RT_ERR_ARG, "rt_closest_points_host: null or empty scene arrays");
+    if (n > 0 && (!points || !hits)) return set_error(RT_ERR_ARG, "rt_closest_points_host: null points or hits");
+    if (n > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_closest_points_host: more than 2^31-1 points");
+    struct Leaf {
+        f3 a, e1, e2;
+        BoxP box;
+        int32_t tri;
+    };
+    std::vector<Leaf> leaves;
+    for (size_t j = P - 1; j < 2 * P - 1; ++j) {
+        if (nodes[j].object_idx >= P) continue;  // names no triangle: contributes nothing
+        const rt_triangle& T = tris[nodes[j].object_idx];
+        const rt_aabb& b = aabbs[j];
+        const f3 v0 = mk(T.v0.x, T.v0.y, T.v0.z);
+        leaves.push_back(Leaf{v0, sub(mk(T.v1.x, T.v1.y, T.v1.z), v0), sub(mk(T.v2.x, T.v2.y, T.v2.z), v0),
+                              BoxP{(v2f){b.min_corner.x, b.max_corner.x}, (v2f){b.min_corner.y, b.max_corner.y},
+                                   (v2f){b.min_corner.z, b.max_corner.z}},
+                              int32_t(nodes[j].object_idx)});
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const f3 q = mk(points[3 * i], points[3 * i + 1], points[3 * i + 2]);
+        CpHit best = cp_start(max_d2 ? max_d2[i] : INFINITY);
+        for (const Leaf& L : leaves) {
+            const CpHit c = cp_triangle(q, L.a, L.e1, L.e2, L.box, L.tri);
+            if (cp_wins(c, best)) best = c;
+        }
+        rt_point_hit h = {-1, -1.0f, {0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, -1};
+        if (best.region >= 0) h = {best.tri, best.D, {best.p.x, best.p.y, best.p.z}, best.v, best.w, best.region};
+        std::memcpy(&hits[i], &h, sizeof(h));
+        if (evals) evals[i] = uint32_t(leaves.size());
     }
     return RT_OK;
 }
