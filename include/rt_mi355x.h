@@ -57,7 +57,8 @@ extern "C" {
                                  RT_MULTI_HIT_MAX_K, rt_trace_multi_hits, rt_trace_multi_hits_device,
                                  rt_trace_multi_hits_variant, rt_multi_hits_host; rt_point_hit,
                                  rt_closest_points, rt_closest_points_device,
-                                 rt_closest_points_variant, rt_closest_points_host */
+                                 rt_closest_points_variant, rt_closest_points_host;
+                                 rt_debug_query_variant */
 
 enum {
     RT_OK = 0,
@@ -1252,6 +1253,11 @@ int rt_debug_scene_refit_pack(size_t P, const rt_bvh_node* nodes, const rt_aabb*
 /* ... with n refits in turn: poses[0], then poses[1], ... (P triangles each). */
 int rt_debug_scene_refit_chain(size_t P, const rt_bvh_node* nodes, const rt_aabb* aabbs, const rt_triangle* tris,
                                int n, const rt_triangle* const* poses, int64_t info[21], uint64_t digests[22]);
+/* The variant rule of the caller queries (rt_trace_rays_variant and the other rt_*_variant), on
+ * the facts of a scene it reads (rt_debug_scene_pack's info[4..7]) and a call's flags (no device):
+ * RT_RAYS_VARIANT_DEEP when deep; else WIDE when wide and lane_wide without RT_FLAG_BINARY; else
+ * BINARY when lane_stack; else DEEP. */
+int rt_debug_query_variant(int wide, int lane_stack, int lane_wide, int deep, int flags);
 
 /* Durations (ms) of the render kernel of the most recent min(max, launches, 256) timed
  * rt_render_device calls on this scene, oldest first, measured with HIP events recorded

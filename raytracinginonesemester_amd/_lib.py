@@ -296,6 +296,7 @@ SIGNATURES = {
     "rt_debug_scene_digest": (I, [P, P, P]),
     "rt_debug_scene_refit_pack": (I, [SZ, P, P, P, P, P, P]),
     "rt_debug_scene_refit_chain": (I, [SZ, P, P, P, I, P, P, P]),
+    "rt_debug_query_variant": (I, [I, I, I, I, I]),
     "rt_powf_batch": (I, [I, P, P, I, P]),
     "rt_box_test_host": (I, [P, P, P, I, P, P, P]),
     "rt_box_test_batch": (I, [I, P, P, P, P, P, I, P]),

@@ -270,7 +270,7 @@ class DeviceScene:
         HIP-event ms of its launches.  Only for scenes made with ``refittable=True``."""
         ms = C.c_float(0.0)
         P = self.num_triangles
-        if type(triangles).__module__.split(".")[0] == "torch":
+        if _is_torch(triangles):
             import torch
 
             dev = torch.device("cuda", self.device)
@@ -302,7 +302,7 @@ class DeviceScene:
         P = self.num_triangles
         NN = 2 * P - 1
         nodes = aabbs = None
-        if type(triangles).__module__.split(".")[0] == "torch":
+        if _is_torch(triangles):
             import torch
 
             dev = torch.device("cuda", self.device)
@@ -358,6 +358,14 @@ class DeviceScene:
         """(rays in key order, order) for a query's ``sort=`` ("origin", "origin_dir" or True, the
         measured default) on the device path: the scene's box, the mode's default bits."""
         return sort_rays(rays, self.bounds(), SORT_DEFAULT if sort is True else sort, None, stream)
+
+    def _sort_query(self, rays, sort, stream, *side):
+        """A query's ``sort=`` prologue on the device path: (rays, order, *side), the rays sorted and
+        the per-ray ``side`` tensors (None allowed) gathered; as given, with order None, without a sort."""
+        if sort is None or sort is False or rays.shape[0] == 0:
+            return (rays, None, *side)
+        rays, order = self._sorted_rays(rays, sort, stream)
+        return (rays, order, *(None if a is None else gather(a, order, stream=stream) for a in side))
 
     @property
     def handle(self) -> C.c_void_p:
@@ -496,50 +504,27 @@ class DeviceScene:
             raise ValueError(f"trace_rays: mode must be one of {sorted(modes)}, not {mode!r}")
         m = modes[mode]
         occluded = m == L.RT_RAYS_OCCLUDED
-        if type(rays).__module__.split(".")[0] == "torch":
+        if _is_torch(rays):
             import torch
 
-            dev = torch.device("cuda", self.device)
-            if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
-                raise ValueError(f"trace_rays: expects an (n, 6) float32 tensor on {dev}")
-            if timing:
-                raise ValueError("trace_rays: timing is measured on the host path only")
-            rays = rays.contiguous()
+            dev = self._torch_dev()
+            rays = _query_tensor(rays, 6, dev, "trace_rays", timing)
             n = rays.shape[0]
-            mt = None
-            if max_t is not None:
-                mt = torch.as_tensor(max_t, dtype=torch.float32, device=dev).contiguous()
-                if mt.shape != (n,):
-                    raise ValueError("trace_rays: max_t must hold one float per ray")
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            order = None
-            if sort is not None and sort is not False and n > 0:
-                rays, order = self._sorted_rays(rays, sort, stream)
-                if mt is not None:
-                    mt = gather(mt, order, stream=stream)
+            mt = _per_item(max_t, n, dev, "trace_rays", "max_t", "ray")
+            stream = _stream_of(stream, dev)
+            rays, order, mt = self._sort_query(rays, sort, stream, mt)
             idx = torch.empty(n, dtype=torch.int32, device=dev)
             t = None if occluded else torch.empty(n, dtype=torch.float32, device=dev)
             check(lib().rt_trace_rays_device(self._handle(), m, rays.data_ptr(), None if mt is None else mt.data_ptr(),
                                              n, int(flags), idx.data_ptr(), None if t is None else t.data_ptr(),
                                              stream))
-            if order is not None:
-                tmp = (rays, order, mt, idx, t)
-                idx = scatter(idx, order, stream=stream)
-                t = None if t is None else scatter(t, order, stream=stream)
-                _used_on(stream, dev, *tmp)
+            idx, t = _unsort(order, stream, dev, (rays, mt), idx, t)
             return idx != 0 if occluded else (idx, t)
         if sort is not None and sort is not False:
             raise ValueError("trace_rays: sort is for the device path (torch tensors) only")
-        r = _c(rays, np.float32)
-        if r.ndim != 2 or r.shape[1] != 6:
-            raise ValueError("trace_rays: expects an (n, 6) array of origins and directions")
+        r = _query_array(rays, 6, "trace_rays", "origins and directions")
         n = r.shape[0]
-        mt = None
-        if max_t is not None:
-            mt = _c(max_t, np.float32)
-            if mt.shape != (n,):
-                raise ValueError("trace_rays: max_t must hold one float per ray")
+        mt = _per_item(max_t, n, None, "trace_rays", "max_t", "ray")
         idx = np.zeros(n, np.int32)
         t = None if occluded else np.zeros(n, np.float32)
         ms = C.c_float(0.0)
@@ -571,52 +556,27 @@ class DeviceScene:
         o.max_depth, o.diffuse_bounce = int(max_depth), 1 if diffuse_bounce else 0
         o.miss_color = _v3(miss_color)
         o.flags = int(flags)
-        if type(rays).__module__.split(".")[0] == "torch":
+        if _is_torch(rays):
             import torch
 
-            dev = torch.device("cuda", self.device)
-            if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
-                raise ValueError(f"shade_rays: expects an (n, 6) float32 tensor on {dev}")
-            if timing:
-                raise ValueError("shade_rays: timing is measured on the host path only")
-            rays = rays.contiguous()
+            dev = self._torch_dev()
+            rays = _query_tensor(rays, 6, dev, "shade_rays", timing)
             n = rays.shape[0]
-            sd = None
-            if seeds is not None:
-                if type(seeds).__module__.split(".")[0] == "torch":
-                    # (uint32 tensors have few torch ops: int32 tensors carry the same 32 bits)
-                    if seeds.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or seeds.device != dev:
-                        raise ValueError(f"shade_rays: seeds must be an int32 or uint32 tensor on {dev}")
-                    sd = seeds.contiguous()
-                else:
-                    sd = torch.from_numpy(_c(seeds, np.uint32).view(np.int32)).to(dev)
-                if tuple(sd.shape) != (n,):
-                    raise ValueError("shade_rays: seeds must hold one uint32 per ray")
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            order = None
-            if sort is not None and sort is not False and n > 0:
-                rays, order = self._sorted_rays(rays, sort, stream)
-                if sd is not None:
-                    sd = gather(sd.view(torch.int32), order, stream=stream)
+            sd = _seed_tensor(seeds, n, dev, "shade_rays", "ray")
+            stream = _stream_of(stream, dev)
+            # (uint32 tensors have few torch ops: int32 tensors carry the same 32 bits)
+            rays, order, sd = self._sort_query(rays, sort, stream, None if sd is None else sd.view(torch.int32))
             rad = torch.empty((n, 3), dtype=torch.float32, device=dev)
             idx = torch.empty(n, dtype=torch.int32, device=dev) if aov else None
             t = torch.empty(n, dtype=torch.float32, device=dev) if aov else None
             check(lib().rt_shade_rays_device(self._handle(), rays.data_ptr(), None if sd is None else sd.data_ptr(), n,
                                              C.byref(o), rad.data_ptr(), None if idx is None else idx.data_ptr(),
                                              None if t is None else t.data_ptr(), stream))
-            if order is not None:
-                tmp = (rays, order, sd, rad, idx, t)
-                rad = scatter(rad, order, stream=stream)
-                if aov:
-                    idx, t = scatter(idx, order, stream=stream), scatter(t, order, stream=stream)
-                _used_on(stream, dev, *tmp)
+            rad, idx, t = _unsort(order, stream, dev, (rays, sd), rad, idx, t)
             return (rad, idx, t) if aov else rad
         if sort is not None and sort is not False:
             raise ValueError("shade_rays: sort is for the device path (torch tensors) only")
-        r = _c(rays, np.float32)
-        if r.ndim != 2 or r.shape[1] != 6:
-            raise ValueError("shade_rays: expects an (n, 6) array of origins and directions")
+        r = _query_array(rays, 6, "shade_rays", "origins and directions")
         n = r.shape[0]
         sd = None
         if seeds is not None:
@@ -763,33 +723,20 @@ class DeviceScene:
         synchronisation, and one (n, 16) int32 tensor is returned, the records' 32-bit words
         (hit_fields names them).  ``flags``: RT_FLAG_BINARY or 0.  ``sort``: as for trace_rays (rays
         sorted, the records scattered back)."""
-        if type(rays).__module__.split(".")[0] == "torch":
+        if _is_torch(rays):
             import torch
 
-            dev = torch.device("cuda", self.device)
-            if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
-                raise ValueError(f"trace_hits: expects an (n, 6) float32 tensor on {dev}")
-            if timing:
-                raise ValueError("trace_hits: timing is measured on the host path only")
-            rays = rays.contiguous()
+            dev = self._torch_dev()
+            rays = _query_tensor(rays, 6, dev, "trace_hits", timing)
             n = rays.shape[0]
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            order = None
-            if sort is not None and sort is not False and n > 0:
-                rays, order = self._sorted_rays(rays, sort, stream)
+            stream = _stream_of(stream, dev)
+            rays, order = self._sort_query(rays, sort, stream)
             hits = torch.empty((n, 16), dtype=torch.int32, device=dev)
             check(lib().rt_trace_hits_device(self._handle(), rays.data_ptr(), n, int(flags), hits.data_ptr(), stream))
-            if order is not None:
-                tmp = (rays, order, hits)
-                hits = scatter(hits, order, stream=stream)
-                _used_on(stream, dev, *tmp)
-            return hits
+            return _unsort(order, stream, dev, (rays,), hits)[0]
         if sort is not None and sort is not False:
             raise ValueError("trace_hits: sort is for the device path (torch tensors) only")
-        r = _c(rays, np.float32)
-        if r.ndim != 2 or r.shape[1] != 6:
-            raise ValueError("trace_hits: expects an (n, 6) array of origins and directions")
+        r = _query_array(rays, 6, "trace_hits", "origins and directions")
         n = r.shape[0]
         hits = np.zeros(n, HIT_DTYPE)
         ms = C.c_float(0.0)
@@ -820,23 +767,14 @@ class DeviceScene:
         k = int(k)
         if not 0 <= k <= L.RT_MULTI_HIT_MAX_K:
             raise ValueError(f"trace_multi_hits: k must be in 0..{L.RT_MULTI_HIT_MAX_K}")
-        if type(rays).__module__.split(".")[0] == "torch":
+        if _is_torch(rays):
             import torch
 
-            dev = torch.device("cuda", self.device)
-            if rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6:
-                raise ValueError(f"trace_multi_hits: expects an (n, 6) float32 tensor on {dev}")
-            if timing:
-                raise ValueError("trace_multi_hits: timing is measured on the host path only")
-            rays = rays.contiguous()
+            dev = self._torch_dev()
+            rays = _query_tensor(rays, 6, dev, "trace_multi_hits", timing)
             n = rays.shape[0]
-            mt = None
-            if max_t is not None:
-                mt = torch.as_tensor(max_t, dtype=torch.float32, device=dev).contiguous()
-                if mt.shape != (n,):
-                    raise ValueError("trace_multi_hits: max_t must hold one float per ray")
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
+            mt = _per_item(max_t, n, dev, "trace_multi_hits", "max_t", "ray")
+            stream = _stream_of(stream, dev)
             count = torch.empty(n, dtype=torch.int32, device=dev)
             rec = torch.empty((n, k, 4), dtype=torch.int32, device=dev)
             if n > 0:  # (an empty tensor has no address to pass)
@@ -846,15 +784,9 @@ class DeviceScene:
             _used_on(stream, dev, rays, mt)
             f = rec.view(torch.float32)
             return count, rec[:, :, 0], f[:, :, 1], f[:, :, 2], f[:, :, 3]
-        r = _c(rays, np.float32)
-        if r.ndim != 2 or r.shape[1] != 6:
-            raise ValueError("trace_multi_hits: expects an (n, 6) array of origins and directions")
+        r = _query_array(rays, 6, "trace_multi_hits", "origins and directions")
         n = r.shape[0]
-        mt = None
-        if max_t is not None:
-            mt = _c(max_t, np.float32)
-            if mt.shape != (n,):
-                raise ValueError("trace_multi_hits: max_t must hold one float per ray")
+        mt = _per_item(max_t, n, None, "trace_multi_hits", "max_t", "ray")
         count = np.zeros(n, np.int32)
         rec = np.zeros((n, k), MULTI_HIT_DTYPE)
         ms = C.c_float(0.0)
@@ -892,23 +824,14 @@ class DeviceScene:
         path: one launch on ``stream`` (a HIP stream handle; default torch's current stream), no
         host synchronisation, tensors returned (views of one (n, 8) record tensor).  ``flags``:
         RT_FLAG_BINARY or 0."""
-        if type(points).__module__.split(".")[0] == "torch":
+        if _is_torch(points):
             import torch
 
-            dev = torch.device("cuda", self.device)
-            if points.device != dev or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-                raise ValueError(f"closest_points: expects an (n, 3) float32 tensor on {dev}")
-            if timing:
-                raise ValueError("closest_points: timing is measured on the host path only")
-            points = points.contiguous()
+            dev = self._torch_dev()
+            points = _query_tensor(points, 3, dev, "closest_points", timing)
             n = points.shape[0]
-            md = None
-            if max_d2 is not None:
-                md = torch.as_tensor(max_d2, dtype=torch.float32, device=dev).contiguous()
-                if md.shape != (n,):
-                    raise ValueError("closest_points: max_d2 must hold one float per point")
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
+            md = _per_item(max_d2, n, dev, "closest_points", "max_d2", "point")
+            stream = _stream_of(stream, dev)
             rec = torch.empty((n, 8), dtype=torch.int32, device=dev)
             ev = torch.empty(n, dtype=torch.int32, device=dev) if evals else None
             if n > 0:  # (an empty tensor has no address to pass)
@@ -919,15 +842,9 @@ class DeviceScene:
             f = rec.view(torch.float32)
             out = (rec[:, 0], f[:, 1], f[:, 2:5], f[:, 5], f[:, 6], rec[:, 7])
             return (*out, ev) if evals else out
-        q = _c(points, np.float32)
-        if q.ndim != 2 or q.shape[1] != 3:
-            raise ValueError("closest_points: expects an (n, 3) array of points")
+        q = _query_array(points, 3, "closest_points", "points")
         n = q.shape[0]
-        md = None
-        if max_d2 is not None:
-            md = _c(max_d2, np.float32)
-            if md.shape != (n,):
-                raise ValueError("closest_points: max_d2 must hold one float per point")
+        md = _per_item(max_d2, n, None, "closest_points", "max_d2", "point")
         rec = np.zeros(n, POINT_HIT_DTYPE)
         ev = np.zeros(n, np.uint32) if evals else None
         ms = C.c_float(0.0)
@@ -1543,7 +1460,7 @@ class Film:
     def _stream(self, stream):
         import torch
 
-        return torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream if stream is None else stream
+        return _stream_of(stream, torch.device("cuda", self.device))
 
     def add(self, radiance, row0: int = 0, rows: Optional[int] = None, nsamples: Optional[int] = None,
             stream: Optional[int] = None) -> None:
@@ -1659,7 +1576,7 @@ def camera_rays_pixels(camera: Camera, pixels, counts, nsamples: int, jitter, de
     def words(a, who):
         if a is None:
             return None
-        if type(a).__module__.split(".")[0] != "torch":
+        if not _is_torch(a):
             a = torch.from_numpy(_c(a, np.uint32).view(np.int32)).to(dev)
         if a.device != dev or a.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
             raise ValueError(f"camera_rays_pixels: {who} must be an int32 or uint32 tensor on {dev}")
@@ -1680,7 +1597,7 @@ def camera_rays_pixels(camera: Camera, pixels, counts, nsamples: int, jitter, de
         cp = None if ct is None else ct.data_ptr()
     if isinstance(jitter, (int, np.integer)):
         jitter = jittered_samples(int(jitter))
-    if type(jitter).__module__.split(".")[0] == "torch":
+    if _is_torch(jitter):
         if jitter.device != dev or jitter.dtype != torch.float32 or jitter.numel() % 2 != 0:
             raise ValueError(f"camera_rays_pixels: jitter must be a (table_spp, 2) float32 tensor on {dev}")
         jd = jitter.contiguous()
@@ -1910,6 +1827,51 @@ def _stream_of(stream, dev):
     return torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
 
 
+def _query_tensor(x, width: int, dev, who: str, timing: bool):
+    """The device path's input check: x as a contiguous (n, width) float32 tensor on dev; no timing."""
+    import torch
+
+    if x.device != dev or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != width:
+        raise ValueError(f"{who}: expects an (n, {width}) float32 tensor on {dev}")
+    if timing:
+        raise ValueError(f"{who}: timing is measured on the host path only")
+    return x.contiguous()
+
+
+def _query_array(x, width: int, who: str, noun: str) -> np.ndarray:
+    """The host path's input check: x as a contiguous (n, width) float32 array of ``noun``."""
+    a = _c(x, np.float32)
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError(f"{who}: expects an (n, {width}) array of {noun}")
+    return a
+
+
+def _per_item(x, n: int, dev, who: str, name: str, item: str):
+    """None, or x as n float32 bounds (max_t, max_d2): a tensor on dev, or an array when dev is None."""
+    if x is None:
+        return None
+    if dev is None:
+        a = _c(x, np.float32)
+    else:
+        import torch
+
+        a = torch.as_tensor(x, dtype=torch.float32, device=dev).contiguous()
+    if tuple(a.shape) != (n,):
+        raise ValueError(f"{who}: {name} must hold one float per {item}")
+    return a
+
+
+def _unsort(order, stream, dev, temps, *outs) -> tuple:
+    """A query's ``sort=`` epilogue: ``outs`` (None allowed) scattered back to the caller's order;
+    the sorted tensors, ``temps`` and ``order`` among them, are dropped on return (_used_on).
+    ``outs`` as given when order is None."""
+    if order is None:
+        return outs
+    back = tuple(None if a is None else scatter(a, order, stream=stream) for a in outs)
+    _used_on(stream, dev, order, *temps, *outs)
+    return back
+
+
 def _used_on(stream, dev, *tensors) -> None:
     """Tell torch's allocator that ``tensors``, temporaries a call drops on return, are in use on
     ``stream`` (a HIP stream handle) when that is not torch's current stream, so that their memory
@@ -1924,20 +1886,20 @@ def _used_on(stream, dev, *tensors) -> None:
             t.record_stream(ext)
 
 
-def _seed_tensor(seeds, n: int, dev, who: str):
+def _seed_tensor(seeds, n: int, dev, who: str, item: str = "path"):
     """n uint32 seeds as an int32 tensor on dev (the same 32 bits), or None."""
     import torch
 
     if seeds is None:
         return None
-    if type(seeds).__module__.split(".")[0] == "torch":
+    if _is_torch(seeds):
         if seeds.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or seeds.device != dev:
             raise ValueError(f"{who}: seeds must be an int32 or uint32 tensor on {dev}")
         sd = seeds.contiguous()
     else:
         sd = torch.from_numpy(_c(seeds, np.uint32).view(np.int32)).to(dev)
     if tuple(sd.shape) != (n,):
-        raise ValueError(f"{who}: seeds must hold one uint32 per path")
+        raise ValueError(f"{who}: seeds must hold one uint32 per {item}")
     return sd
 
 
@@ -2271,10 +2233,8 @@ def build_bvh_device(positions, indices, device: int = 0, stream=None, tensors: 
     P = idx.shape[0]
     nodes = torch.empty((max(2 * P - 1, 1), 4), dtype=torch.int32, device=dev)
     aabbs = torch.empty((max(2 * P - 1, 1), 6), dtype=torch.float32, device=dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
     check(lib().rt_build_bvh_device(device, pos.data_ptr(), pos.shape[0], idx.data_ptr(), P, nodes.data_ptr(),
-                                    aabbs.data_ptr(), stream))
+                                    aabbs.data_ptr(), _stream_of(stream, dev)))
     if tensors:
         return nodes, aabbs
     return nodes.cpu().numpy().view(np.uint32), aabbs.cpu().numpy()
@@ -2345,7 +2305,7 @@ def encode_p6_device(rgb, maxval=255, clamp=True, gamma2=True, flip_y=False):
     H, W = rgb.shape[0], rgb.shape[1]
     bps = 1 if maxval < 256 else 2
     body = torch.empty(H * W * 3 * bps, dtype=torch.uint8, device=rgb.device)
-    stream = torch.cuda.current_stream(rgb.device).cuda_stream
+    stream = _stream_of(None, rgb.device)
     quantize_p6_device(rgb.data_ptr(), W, H, body.data_ptr(), maxval, clamp, gamma2, flip_y, stream)
     return p6_header(W, H, maxval) + body.cpu().numpy().tobytes()
 

@@ -5,7 +5,8 @@
 * librt_mi355x.so — the host units rt_host.cpp, rt_records.cpp and rt_scene_pack.cpp (g++; the
   last is rt_scene_create's host half: checks, ids, stack bounds and every packed array) + the
   device translation units (hipcc --offload-arch=gfx950): rt_device.hip (scene upload + render;
-  its device code in the rt_wave/instrument/traverse/shade/prepass/query/multihit/closest/path/refit/rebuild.hpp sections),
+  its device code in the rt_wave/instrument/traverse/shade/prepass/query/multihit/closest/path/refit/rebuild.hpp sections,
+  the host side of the caller queries in the rt_query_host.hpp section),
   rt_hw1.hip (the HW1 path),
   rt_frame.hip (P6 quantisation, strip un-permute, the film and the adaptive film on the device), rt_lbvh.hip (LBVH build on
   the device), rt_renderer.hip (the multi-GPU frame renderer), rt_raysort.hip (ray keys, the

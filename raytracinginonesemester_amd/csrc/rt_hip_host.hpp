@@ -1,5 +1,6 @@
 // rt_hip_host.hpp — host-side HIP helpers shared by the device translation units
-// (error mapping into the C ABI's RT_ERR_HIP, owned device buffers, gfx950 check).
+// (error mapping into the C ABI's RT_ERR_HIP, owned device buffers, the event pair of a timed
+// span, the staged form of a query, gfx950 check).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,6 +38,78 @@ struct DevBuf {
         if (rc != RT_OK || bytes == 0) return rc;
         hipError_t e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) return set_error(RT_ERR_HIP, hip_msg(e, "hipMemcpy H2D"));
+        return RT_OK;
+    }
+};
+
+// The HIP-event time of a span of one stream, for the entries that report one through an optional
+// float*: every method does nothing when on is false (the caller passed no float*).
+struct KernelTimer {
+    bool on;
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit KernelTimer(bool want) : on(want) {}
+    KernelTimer(const KernelTimer&) = delete;
+    KernelTimer& operator=(const KernelTimer&) = delete;
+    ~KernelTimer() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    int start(hipStream_t st) {  // creates both events, records the first
+        if (!on) return RT_OK;
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        HIP_TRY(hipEventRecord(a, st));
+        return RT_OK;
+    }
+    int stop(hipStream_t st) {
+        if (on) HIP_TRY(hipEventRecord(b, st));
+        return RT_OK;
+    }
+    int read(float* ms) {  // after the stream has been synchronised
+        if (on) HIP_TRY(hipEventElapsedTime(ms, a, b));
+        return RT_OK;
+    }
+};
+
+// The staged (host-array) form of a query: inputs uploaded, then outputs allocated, then one launch
+// on the null stream between the timer's two records, that stream synchronised, the time read and
+// every output copied back.  An absent array (null host pointer) has a null device pointer.  The
+// first error sticks: every later call does nothing and run returns it; the buffers are freed
+// with the object.
+struct Staging {
+    static constexpr int kMax = 6;
+    struct Slot {
+        DevBuf d;
+        void* back = nullptr;  // an output's host array
+    } slot[kMax];
+    int n = 0, rc = RT_OK;
+    Slot* next(const void* host) {
+        if (rc != RT_OK || !host) return nullptr;
+        if (n == kMax) return rc = set_error(RT_ERR_INTERNAL, "Staging: more than kMax arrays"), nullptr;
+        return &slot[n++];
+    }
+    template <class T>
+    const T* in(const T* host, size_t count) {
+        Slot* s = next(host);
+        if (s) rc = s->d.upload(host, count * sizeof(T));
+        return s ? static_cast<const T*>(s->d.p) : nullptr;
+    }
+    template <class T>
+    T* out(T* host, size_t count) {
+        Slot* s = next(host);
+        if (s) s->back = host, rc = s->d.alloc(count * sizeof(T));
+        return s ? static_cast<T*>(s->d.p) : nullptr;
+    }
+    // launch: int(), one *_launch on the null stream with the pointers in() and out() gave
+    template <class Launch>
+    int run(float* kernel_ms, Launch&& launch) {
+        if (rc != RT_OK) return rc;
+        KernelTimer t(kernel_ms != nullptr);
+        if ((rc = t.start(nullptr)) != RT_OK || (rc = launch()) != RT_OK || (rc = t.stop(nullptr)) != RT_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if ((rc = t.read(kernel_ms)) != RT_OK) return rc;
+        for (int i = 0; i < n; ++i)
+            if (slot[i].back) HIP_TRY(hipMemcpy(slot[i].back, slot[i].d.p, slot[i].d.n, hipMemcpyDeviceToHost));
         return RT_OK;
     }
 };

@@ -584,6 +584,13 @@ extern "C" int rt_debug_box_weight_host(const float* boxes, const uint32_t* leav
     return RT_OK;
 }
 
+// SceneMeta::query_variant for the tests: the caller queries' variant rule on the four facts it reads.
+extern "C" int rt_debug_query_variant(int wide, int lane_stack, int lane_wide, int deep, int flags) {
+    rt::SceneMeta m;
+    m.wide = wide != 0, m.lane_stack = lane_stack != 0, m.lane_wide = lane_wide != 0, m.deep = deep != 0;
+    return m.query_variant(flags);
+}
+
 static void digest_pack(const rt::PackedScene& pk, int64_t info[21], uint64_t digests[22]) {
     rt::scene_info_words(pk.meta, pk.binary_stack, pk.wide_stack, info);
     size_t i = 0;

@@ -29,6 +29,20 @@ struct SceneMeta {
     bool deep = false;          // the DFS may need more than STACK_CAP entries: MODE_DEEP kernels
     int f_log2 = 2;             // arity of the frustum records in fnode (2: none, the traversal takes wnode)
     int f_bound = 0;            // their DFS stack bound (<= FRUSTUM_STACK unless RT_TUNE_FRUSTUM_STACK_CAP raised it)
+
+    // The traversal (RT_RAYS_VARIANT_*) every caller query on this scene launches under `flags`.
+    // The first that applies: DEEP for a deep scene; WIDE, else BINARY, where the per-lane stack
+    // of those records fits LDS; else DEEP, which is exact for any tree (a tree that is not deep
+    // needs at most STACK_CAP of its 512 entries, so the brute-force completion, and with it the
+    // absent tri array, is unreachable).
+    int query_variant(int flags) const {
+        int variant = RT_RAYS_VARIANT_DEEP;
+        if (!deep) {
+            if (wide && lane_wide && !(flags & RT_FLAG_BINARY)) variant = RT_RAYS_VARIANT_WIDE;
+            else if (lane_stack) variant = RT_RAYS_VARIANT_BINARY;
+        }
+        return variant;
+    }
 };
 
 struct PackedArray {

@@ -74,6 +74,43 @@ def test_python_mode_names():
         unbound.trace_rays(_RAYS, mode="nearest")
 
 
+# The variant rule of every caller query (rt::SceneMeta::query_variant through rt_debug_query_variant),
+# row by row: (wide, lane_stack, lane_wide, deep) -> (variant with flags 0, with RT_FLAG_BINARY).
+# deep gives DEEP; else wide and lane_wide without the flag give WIDE; else lane_stack gives BINARY;
+# else DEEP.
+_W, _B, _D = L.RT_RAYS_VARIANT_WIDE, L.RT_RAYS_VARIANT_BINARY, L.RT_RAYS_VARIANT_DEEP
+VARIANT_RULE = {
+    (0, 0, 0, 0): (_D, _D),
+    (0, 0, 0, 1): (_D, _D),
+    (0, 0, 1, 0): (_D, _D),  # lane_wide says nothing without the 4-ary records
+    (0, 0, 1, 1): (_D, _D),
+    (0, 1, 0, 0): (_B, _B),
+    (0, 1, 0, 1): (_D, _D),
+    (0, 1, 1, 0): (_B, _B),
+    (0, 1, 1, 1): (_D, _D),
+    (1, 0, 0, 0): (_D, _D),
+    (1, 0, 0, 1): (_D, _D),
+    (1, 0, 1, 0): (_W, _D),  # the flag takes WIDE away and the binary stack does not fit LDS
+    (1, 0, 1, 1): (_D, _D),
+    (1, 1, 0, 0): (_B, _B),
+    (1, 1, 0, 1): (_D, _D),
+    (1, 1, 1, 0): (_W, _B),  # frog
+    (1, 1, 1, 1): (_D, _D),
+}
+
+
+def test_variant_rule_row_by_row():
+    assert "rt_debug_query_variant" in L.SIGNATURES
+    assert (_W, _B, _D) == (1, 2, 3) and len(VARIANT_RULE) == 16
+    for facts, want in VARIANT_RULE.items():
+        got = tuple(L.lib().rt_debug_query_variant(*facts, flags) for flags in (0, L.RT_FLAG_BINARY))
+        assert got == want, (facts, got, want)
+    # any non-zero int is true, and only the BINARY bit of flags is read
+    assert L.lib().rt_debug_query_variant(7, -1, 2, 0, 0) == _W
+    assert L.lib().rt_debug_query_variant(1, 1, 1, 0, L.RT_FLAG_BINARY | 8) == _B
+    assert L.lib().rt_debug_query_variant(1, 1, 1, 0, 8) == _W
+
+
 HIT_FRACTION = {"sphere_single": 0.398, "frog": 0.272, "cornell": 0.710, "chain24": 0.498, "chain48": 0.525,
                 "chain300": 0.548, "chain600": 0.550}
 TIE_WINNERS = {"chain24": (162, 58), "chain48": (150, 56), "chain300": (114, 49), "chain600": (26, 132)}
