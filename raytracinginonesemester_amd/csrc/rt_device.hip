@@ -71,6 +71,7 @@
 #include "rt_math.hpp"
 #include "rt_ppm.hpp"
 #include "rt_scene_pack.hpp"
+#include "rt_tilediv.hpp"
 
 using namespace rtd;
 
@@ -165,11 +166,13 @@ struct RenderParams {
     int32_t cut_force;    // test every candidate in tile_cut_kernel (no pass-through)
     int32_t nqueues;
     int32_t queue_cap;
+    uint32_t tiles_x_mul;  // tile / tiles_x without the division: TileDiv{tiles_x_mul, tiles_x_shift} (rt_tilediv.hpp)
     float* __restrict__ rgb;
     int32_t* __restrict__ hit_idx;
     float* __restrict__ hit_t;
     uint8_t* __restrict__ p6;  // optional: write_p6-default samples of the pixels (rows*W*3 bytes)
     uint8_t miss_p6[4];        // the culled pixels' samples
+    uint32_t tiles_x_shift;
     // Heavy-first dispatch (speed only, an approximate longest-first schedule): render waves
     // record their duration per tile (tile_cost, 4 x u16 per tile, 10 ns ticks); the next frame's
     // cut pass moves tiles whose last cost is >= heavy_ticks[c] (descending) to list q's class-c
@@ -193,6 +196,9 @@ struct RenderParams {
     uint32_t drain_tag;
     int32_t gate_q8;  // the gate opens when a queue has handed out gate_q8/256 of its items (256: drained)
 };
+// tiles_x_mul and tiles_x_shift sit in two of the struct's alignment holes: every other field,
+// and the kernel arguments after a RenderParams, keep the offsets the pre-pass kernels read
+static_assert(sizeof(RenderParams) == 544, "RenderParams: a field moved");
 
 #include "rt_wave.hpp"
 #include "rt_instrument.hpp"
@@ -263,10 +269,20 @@ __device__ __forceinline__ void samples_tile(const RenderParams& P, int tile, ui
     constexpr int wl = LS != 0 ? 32 : 64;  // lanes that trace
     const bool on = (t & 63) < wl;
     const int lt = ((int)qw * wl) | (t & (wl - 1));
+    bool all_miss = false;  // wave-uniform, known after the shading
     {
         const int s = lt & (P.spp - 1);  // spp and tile_w are powers of two here
         const int pit = lt >> P.spp_log2;
-        const int tx = tile % P.tiles_x, ty = tile / P.tiles_x;
+        // The depth-1 kernels split the tile index by the host's multiplier and shift
+        // (rt_tilediv.hpp); the bounce kernels stay instruction for instruction what they were.
+        int tx, ty;
+        if constexpr (D1) {
+            ty = (int)tile_div((uint32_t)tile, TileDiv{P.tiles_x_mul, P.tiles_x_shift});
+            tx = tile - ty * P.tiles_x;
+        } else {
+            tx = tile % P.tiles_x;
+            ty = tile / P.tiles_x;
+        }
 #ifndef RT_ROW_PIXELS
         // Pixels in Z order inside a square tile (a wave's pixels form a square: 2x2 at 16 spp,
         // more coherent rays than a row of 4); row-major otherwise.  Any order gives the same
@@ -291,18 +307,26 @@ __device__ __forceinline__ void samples_tile(const RenderParams& P, int tile, ui
         // it, or addresses made from it, live (and spilled) across the shading.
         if (s == 0) kpix[t >> P.spp_log2] = pix;
         const int64_t aov = valid && P.hit_idx ? (int64_t)pix * P.spp + s : -1;
+        if constexpr (D1) RT_PHASE_ITEM(park + (wv << 6), (uint32_t)tile * (BLOCK / 64) + qw);
         const f3 c = trace_sample<MODE, D1, LS == 3 ? 2 : 0>(P, valid, x, y, s, aov, park + t,
                                                                              park + (wv << 6));
-        RT_PHASE(P, x, r, 1);
-        // The thread index again, from the wave's index and a lane id the compiler cannot
-        // merge with the first one (mbcnt of a zero read back from LDS): keeping t itself live
-        // across the traversals cost a 4-byte scratch spill per lane (c3: ~8 MB of writes per
-        // launch).
-        const int te = (int)((wv << 6) | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(
-                                                  ~0u, (uint32_t)*(const volatile int*)lds_zero)));
-        col[3 * te] = c.x;
-        col[3 * te + 1] = c.y;
-        col[3 * te + 2] = c.z;
+        if constexpr (D1) RT_PHASE(park + (wv << 6), 1);
+        // A depth-1 wave none of whose lanes hit (spp <= 64: its pixels are its own) has the pixel
+        // the host knows, P.miss_pixel: the same ordered sum of clamp01(miss), then * 1/spp
+        // (miss_pixel_value; the cull pass writes it to the tiles it culls).  Such a wave stores
+        // no samples and sums none.
+        if constexpr (D1) all_miss = P.spp <= 64 && !d1_wave_hit(park + (wv << 6));
+        if (!all_miss) {
+            // The thread index again, from the wave's index and a lane id the compiler cannot
+            // merge with the first one (mbcnt of a zero read back from LDS): keeping t itself live
+            // across the traversals cost a 4-byte scratch spill per lane (c3: ~8 MB of writes per
+            // launch).
+            const int te = (int)((wv << 6) | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(
+                                                      ~0u, (uint32_t)*(const volatile int*)lds_zero)));
+            col[3 * te] = c.x;
+            col[3 * te + 1] = c.y;
+            col[3 * te + 2] = c.z;
+        }
     }
     const int t2 = (int)((wv << 6) | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(
                                              ~0u, (uint32_t)*(const volatile int*)lds_zero)));
@@ -314,7 +338,61 @@ __device__ __forceinline__ void samples_tile(const RenderParams& P, int tile, ui
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     } else {
-        __syncthreads();
+        __syncthreads();  // a pixel's samples span the block's waves
+    }
+    // The depth-1 kernels' wave-level epilogue; the bounce kernels keep the sum below.
+    if (D1 && P.spp <= 64) {
+        // One lane per (channel, pixel of the wave): 12 lanes at 16 spp, each adding its
+        // channel's samples in sample order (col = col + TraceRayIterative(...), then col /
+        // float(spp)): the additions and their order are those of one lane per pixel.
+        const int ppw_log2 = 6 - P.spp_log2;  // pixels per wave
+        // 1 / spp, exact: spp is a power of two here.  x / 2^k and x * 2^-k are the same
+        // correctly rounded value (the exact quotients are equal), so the divide is a multiply.
+        const float rs = __int_as_float((127 - P.spp_log2) << 23);
+        for (int i = t2 & 63; i < (3 << ppw_log2); i += 64) {
+            const int ch = i >> ppw_log2, pw = i & ((1 << ppw_log2) - 1);
+            const int pix = kpix[(int)(wv << ppw_log2) + pw];
+            if (pix < 0) continue;
+            const size_t k = (size_t)pix * 3 + ch;
+            if (all_miss) {
+                // the three values as scalars, the lane's chosen among them (a select between the
+                // fields themselves became a per-lane load from the argument segment)
+                const uint32_t m0 = uni((uint32_t)__float_as_int(P.miss_pixel.x)),
+                               m1 = uni((uint32_t)__float_as_int(P.miss_pixel.y)),
+                               m2 = uni((uint32_t)__float_as_int(P.miss_pixel.z));
+                uint32_t b;  // the four bytes as one word (a scalar load; single bytes load per lane)
+                __builtin_memcpy(&b, P.miss_p6, sizeof(b));
+                b = uni(b);
+                if (P.rgb) P.rgb[k] = __int_as_float((int)(ch == 0 ? m0 : ch == 1 ? m1 : m2));
+                if (P.p6) P.p6[k] = (uint8_t)(b >> (8 * ch));
+                continue;
+            }
+            const float* sp = col + 3 * (int)((wv << 6) + ((uint32_t)pw << P.spp_log2)) + ch;
+            // the samples are read sixteen (four) at a time and then added in order: one LDS round
+            // trip per group instead of one per sample
+            float acc = 0.f;
+            int j = 0;
+            for (; j + 16 <= P.spp; j += 16) {
+                float s[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) s[u] = sp[3 * (j + u)];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) acc = acc + s[u];
+            }
+            for (; j + 4 <= P.spp; j += 4) {
+                float s[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) s[u] = sp[3 * (j + u)];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) acc = acc + s[u];
+            }
+            for (; j < P.spp; ++j) acc = acc + sp[3 * j];
+            const float v = acc * rs;
+            if (P.rgb) P.rgb[k] = v;
+            if (P.p6) P.p6[k] = rtp::p6_default_sample(v);  // the frame epilogue fused in (write_p6 defaults)
+        }
+        if constexpr (D1) RT_PHASE(park + (wv << 6), 3);
+        return;
     }
     if ((t2 & (P.spp - 1)) == 0) {
         const int pix = kpix[t2 >> P.spp_log2];
@@ -340,6 +418,7 @@ __device__ __forceinline__ void samples_tile(const RenderParams& P, int tile, ui
             }
         }
     }
+    if constexpr (D1) RT_PHASE(park + (wv << 6), 3);
 }
 
 // General spp: one pixel per lane looping over its samples in order (query.cu:146-163).
@@ -352,6 +431,7 @@ __device__ __forceinline__ void pixels_tile(const RenderParams& P, int tile, uin
     const bool valid = x < P.W && r < P.rows;
     const int y = valid ? global_row(P, r) : 0;
     f3 acc = mk(0.f, 0.f, 0.f);
+    if constexpr (D1) RT_PHASE_ITEM(park + (uni((uint32_t)tid) & ~63u), (uint32_t)tile * (BLOCK / 64) + qw);
     for (int s = 0; s < P.spp; ++s) {
         const int64_t aov = valid && P.hit_idx ? ((int64_t)r * P.W + x) * P.spp + s : -1;
         acc = add(acc, trace_sample<MODE, D1>(P, valid, x, y, s, aov, park + tid, park + (uni((uint32_t)tid) & ~63u)));
@@ -2109,6 +2189,11 @@ int render_frame(rt_scene* s, const rt_camera* cam, const rt_render_opts* o, flo
     P.tile_w_log2 = __builtin_ctz(unsigned(tw));
     P.spp_log2 = samples ? __builtin_ctz(unsigned(o->spp)) : 0;
     P.tiles_x = (W + tw - 1) / tw;
+    {
+        const TileDiv td = tile_div_make((uint32_t)P.tiles_x);
+        P.tiles_x_mul = td.mul;
+        P.tiles_x_shift = td.shift;
+    }
     const int tiles_y = (rows + th - 1) / th;
     P.tiles_total = P.tiles_x * tiles_y;
     P.lane_samples = samples ? 1 : 0;

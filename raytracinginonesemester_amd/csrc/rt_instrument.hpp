@@ -22,20 +22,28 @@ __device__ unsigned long long g_rt_stats[24];
 __device__ unsigned long long* g_frame_span;
 #endif
 #ifdef RT_WAVE_TIMES  // instrumented variant builds only: per-wave start / end (wall clock, 100 MHz),
-// per-wave phase ends (primary traversal, whole sample) and per tile the number of cut boxes
-// its rays may meet (tile_cut_kernel)
+// per-item phase marks and per tile the number of cut boxes its rays may meet (tile_cut_kernel)
 __device__ unsigned long long* g_wave_times;
 __device__ uint32_t* g_wave_meta;  // per item: block << 8 | XCC << 4 | first item << 2 | wave in block
+// Four marks per item (tile * waves per tile + quarter, g_wave_times' key) of the depth-1
+// kernels: [0] the primary traversal's end, [1] the whole sample's end (trace_sample returns),
+// [2] just before traverse_camera (item start to here: the item's setup), [3] after the pixel
+// write ([1] to here: the epilogue).  The item's key waits in the wave's LDS (park slot 14, which
+// only these builds have: PARK_SLOTS, rt_shade.hpp), written and read by lane 0.
 __device__ unsigned long long* g_wave_phase;
 __device__ int* g_cut_counts;
-#define RT_PHASE(P, x, y, k)                                                                           \
+#define RT_PHASE_ITEM(park_wave, item)                                                                 \
+    do {                                                                                               \
+        if (lane_id() == 0) (park_wave)[14 * BLOCK] = __int_as_float((int)(item));                     \
+    } while (0)
+#define RT_PHASE(park_wave, k)                                                                         \
     do {                                                                                               \
         if (g_wave_phase && lane_id() == 0)                                                            \
-            g_wave_phase[(((size_t)((y) / (P).tile_h) * (P).tiles_x + (x) / (P).tile_w) * 4 + threadIdx.x / 64) * 2 + (k)] = \
-                wall_clock64();                                                                        \
+            g_wave_phase[(size_t)(uint32_t)__float_as_int((park_wave)[14 * BLOCK]) * 4 + (k)] = wall_clock64(); \
     } while (0)
 #else
-#define RT_PHASE(P, x, y, k) do { } while (0)
+#define RT_PHASE_ITEM(park_wave, item) do { } while (0)
+#define RT_PHASE(park_wave, k) do { } while (0)
 #endif
 
 #ifdef RT_LANE_ITERS  // instrumented variant builds only (with RT_WAVE_TIMES): per work item, the

@@ -84,7 +84,11 @@ __device__ __forceinline__ RayPre camera_ray(const RenderParams& P, bool valid, 
 // of arrays with stride BLOCK): the traversal needs every VGPR the kernel's occupancy allows, and
 // values kept live across it were spilled to scratch (private memory through L2/HBM); LDS is a
 // few tens of cycles away and otherwise unused by the render kernels.
+#ifdef RT_WAVE_TIMES
+constexpr int PARK_SLOTS = 15;  // slot 14: the item's key for the phase marks (rt_instrument.hpp)
+#else
 constexpr int PARK_SLOTS = 14;
+#endif
 struct Park {
     // the wave's slot 0 (LDS, wave-uniform); a lane's slot is found afresh at every access (a
     // per-lane pointer kept across the traversals was itself spilled in the 64-VGPR build)
@@ -116,7 +120,12 @@ __device__ __forceinline__ f3 shade_d1(const RenderParams& P, bool valid_in, con
         if (hit) radiance = add(radiance, mul(mk(1.f, 1.f, 1.f), Lo));
         return clamp01(radiance);
     };
-    if (ballot(hit) == 0) return radiance_of(mk(0.f, 0.f, 0.f));
+    if (ballot(hit) == 0) {
+        // no lane hit: slot 10 says so to the caller (d1_wave_hit), which then takes the
+        // host's all-miss pixel instead of summing these samples
+        pk.put(10, __int_as_float(0));
+        return radiance_of(mk(0.f, 0.f, 0.f));
+    }
     int32_t slot = hs.slot;
     // valid and hit go to LDS at once (slot 10; lit, known later, to slot 11): kept live
     // across the shading, the lane's valid bit was spilled to scratch in the 64-VGPR build
@@ -201,6 +210,15 @@ __device__ __forceinline__ f3 shade_d1(const RenderParams& P, bool valid_in, con
         for (int li = 0; li < sc.num_lights; ++li) light(li);
     }
     return radiance_of(Lo);
+}
+
+// Whether a lane of the wave hit in the shade_d1 call just made, read back from slot 10 (every
+// lane wrote its own word there): a wave-wide value kept in registers across the shading would
+// be live through the shadow traversal.
+__device__ __forceinline__ bool d1_wave_hit(float* park_wave) {
+    const Park pk{park_wave};
+    Park::fence();
+    return ballot((__float_as_int(pk.get(10)) & 2) != 0) != 0;
 }
 
 
@@ -580,10 +598,11 @@ __device__ __forceinline__ f3 trace_sample(const RenderParams& P, bool valid, in
         pk.put(13, __int_as_float((int32_t)(aov >> 32)));
         Park::fence();
         HitState hs;
+        RT_PHASE(park_wave, 2);
         traverse_camera<MODE>(sc, ray, valid, hs);
         Park::fence();
         aov = (int64_t)(uint32_t)__float_as_int(pk.get(12)) | ((int64_t)__float_as_int(pk.get(13)) << 32);
-        RT_PHASE(P, x, y, 0);
+        RT_PHASE(park_wave, 0);
 #ifdef RT_STATS
         if constexpr (MODE != RT_KERNEL_LANE && (MODE & MODE_DEEP) == 0) {
             if (ballot(valid) != 0 && ballot(valid && hs.slot >= 0) == 0) {

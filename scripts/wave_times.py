@@ -1,7 +1,10 @@
 """Per-wave timeline of the c3 render kernel from the RT_WAVE_TIMES variant build
 (scripts/build_variant.sh wavetimes -DRT_WAVE_TIMES): start/end of every rendering wave
 (wall clock, 10 ns ticks), then the kernel span, the wave-duration distribution, the number of
-waves in flight over time and the longest waves' tiles.
+waves in flight over time and the longest waves' tiles; and the items' phases from the four
+marks of rt_instrument.hpp: setup (item start to just before traverse_camera), the primary
+traversal, the shading (to trace_sample's return) and the epilogue (to the item's end), for all
+items and for the items none of whose samples hit (found from a hit-index frame).
 
     RT_MI355X_LIB=build/variants/wavetimes/librt_mi355x.so python scripts/wave_times.py [--config c3]
 """
@@ -44,7 +47,7 @@ buf = torch.zeros(tiles * 4 * 2, dtype=torch.int64, device="cuda")
 rgb = torch.zeros(H * W * 3, dtype=torch.float32, device="cuda")
 cuts = torch.full((tiles,), -1, dtype=torch.int32, device="cuda")
 assert lib.rt_debug_wave_times_set(C.c_void_p(buf.data_ptr()), C.c_void_p(cuts.data_ptr())) == 0
-phase = torch.zeros(tiles * 4 * 2, dtype=torch.int64, device="cuda")
+phase = torch.zeros(tiles * 4 * 4, dtype=torch.int64, device="cuda")
 lib.rt_debug_wave_phase_set.argtypes = [C.c_void_p]
 assert lib.rt_debug_wave_phase_set(C.c_void_p(phase.data_ptr())) == 0
 st = torch.cuda.current_stream().cuda_stream
@@ -58,7 +61,7 @@ torch.cuda.synchronize()
 kms = float(ds.kernel_times(1)[0])
 t = buf.cpu().numpy().reshape(-1, 2)
 cc = cuts.cpu().numpy()
-ph = phase.cpu().numpy().reshape(-1, 2)
+ph = phase.cpu().numpy().reshape(-1, 4)
 np.savez_compressed(Path(a.out).with_suffix(".npz"), times=t, cut_counts=cc, tiles_x=tiles_x, phase=ph)
 live = np.nonzero(t[:, 1])[0]
 s, e = t[live, 0].astype(np.int64), t[live, 1].astype(np.int64)
@@ -90,8 +93,40 @@ for lo, hi in ((1, 1), (2, 3), (4, 7), (8, 15), (16, 31), (32, 64)):
     if m.any():
         res["cut_count_vs_tile_dur_us"][f"{lo}-{hi}"] = {"tiles": int(m.sum()), "mean": round(float(tdur[lt][m].mean()), 1),
                                                         "p90": round(float(np.percentile(tdur[lt][m], 90)), 1)}
-res["corr_count_dur"] = float(np.corrcoef(c, tdur[lt])[0, 1])
+res["corr_count_dur"] = float(np.corrcoef(c, tdur[lt])[0, 1]) if len(lt) > 1 else 0.0
 res["culled_by_cut"] = int(((cc == 0)).sum())
+# the items' phases (depth-1 sample kernels, square tiles: a quarter is a Z-order run of pixels)
+if cfg["max_depth"] == 1 and spp <= 64 and side == th:
+    lib.rt_debug_wave_times_set(None, None)
+    lib.rt_debug_wave_phase_set(None)
+    _, hi, _ = ds.render(cam, spp=spp, max_depth=1, miss_color=hs.settings["miss_color"], aov=True)
+    pix_hit = (np.asarray(hi).reshape(H, W, spp) >= 0).any(axis=2)
+    ppw = 64 // spp  # pixels per item
+    item_hit = np.zeros(tiles * 4, dtype=bool)
+    for qw in range(4):
+        for j in range(ppw):
+            pit = qw * ppw + j
+            px = (pit & 1) | ((pit >> 1) & 2) | ((pit >> 2) & 4) | ((pit >> 3) & 8)
+            py = ((pit >> 1) & 1) | ((pit >> 2) & 2) | ((pit >> 3) & 4) | ((pit >> 4) & 8)
+            tl = np.unique(live // 4)
+            x, y = (tl % tiles_x) * side + px, (tl // tiles_x) * th + py
+            m = (x < W) & (y < H)
+            item_hit[tl[m] * 4 + qw] |= pix_hit[y[m], x[m]]
+    p = ph[live].astype(np.int64)
+    s0, e0 = t[live, 0].astype(np.int64), t[live, 1].astype(np.int64)
+    ok = (p > 0).all(axis=1)
+    parts = {"setup": p[:, 2] - s0, "primary": p[:, 0] - p[:, 2], "shading": p[:, 1] - p[:, 0],
+             "epilogue": e0 - p[:, 1], "pixel_write": p[:, 3] - p[:, 1], "item": e0 - s0}
+    total = float((e0 - s0)[ok].sum())
+
+    def stats(m):
+        return {k: {"mean_us": round(float(v[m].mean()) * 10e-3, 3), "p50_us": round(float(np.median(v[m])) * 10e-3, 3),
+                    "share_of_wave_us": round(float(v[m].sum()) / total, 4)} for k, v in parts.items()}
+
+    miss = ok & ~item_hit[live]
+    res["phases"] = {"items": int(ok.sum()), "all": stats(ok), "no_hit_items": int(miss.sum()), "no_hit": stats(miss),
+                     "wave_us_total": round(total * 10e-3, 1)}
+    print(json.dumps(res["phases"]))
 Path(a.out).write_text(json.dumps(res, indent=1))
 print(json.dumps(res["cut_count_vs_tile_dur_us"]), res["corr_count_dur"], res["culled_by_cut"])
 print(json.dumps({k: v for k, v in res.items() if k != "longest"}))
