@@ -58,7 +58,11 @@ extern "C" {
                                  rt_trace_multi_hits_variant, rt_multi_hits_host; rt_point_hit,
                                  rt_closest_points, rt_closest_points_device,
                                  rt_closest_points_variant, rt_closest_points_host;
-                                 rt_debug_query_variant */
+                                 rt_debug_query_variant; rt_light_shape, RT_LIGHT_MAX_SHADOW_SAMPLES,
+                                 rt_scene_num_lights, rt_light_visibility_device,
+                                 rt_light_visibility_variant, rt_path_step_vis_device,
+                                 rt_light_samples_host, rt_path_step_vis_host,
+                                 rt_host_scene_light_shapes */
 
 enum {
     RT_OK = 0,
@@ -1017,6 +1021,91 @@ int rt_path_compact_device(int device, size_t m, const uint8_t* alive_dev, const
                            const uint32_t* ids_in_dev, rt_ray* rays_out_dev, uint32_t* ids_out_dev,
                            uint32_t* count_dev, void* scratch_dev, void* hip_stream);
 int rt_path_finish_device(int device, size_t n, float* radiance_dev, void* hip_stream);
+
+/* ---- soft shadows: spherical area lights for the staged path ------------------------------------
+ * The reference's other HW2 fork, C/ (HW2/HW2/CPUOnly), gives a light a `radius` and a number of
+ * `shadow_samples`: its ShadowVisibility (C/include/raytracer.h:121-168) samples a disk at the
+ * light that faces the shaded point, and ShadeDirect multiplies the light's term by the unoccluded
+ * fraction (:195-207).  Here that is two stages of the staged path,
+ *   trace_hits -> rt_light_visibility_device -> rt_path_step_vis_device -> compact,
+ * defined as G/'s ShadeDirect with C/'s ShadowVisibility in place of IsInShadow: random_float() is
+ * rng_next(state) on the path's own state, the occlusion decision and RT_EPS (shader.h:22, 1e-3)
+ * stay G/'s.  Float32, no contraction; dot, unit, divf (v / s per component) and cross are the
+ * reference's operators, as in the step.
+ *
+ * rt_light_shape: one per scene light, in the lights' order.
+ *
+ * rt_light_visibility_device, for entry k < m with path id = ids_dev ? ids_dev[k] : k, when
+ * id != RT_PATH_NONE and hits[k].tri >= 0: p and n come from the record, N = unit(n),
+ * state = rng_dev[id], and each light l in index order is processed by steps 1 to 5:
+ *   1. toC = lpos - p, L = unit(toC), NdotL = fmaxf(dot(N, L), 0) (the step's own expressions).
+ *      NdotL <= 0: vis[k][l] = 0, nothing is drawn, next light.
+ *   2. distC = sqrtf(dot(toC, toC)).  !(distC > 0): vis = 1, nothing is drawn, next light (the
+ *      step casts no ray there and lights the point).
+ *   3. soft = shapes[l].radius > 0 (NaN and negative radii are point lights);
+ *      S = soft ? max(shadow_samples, 1) : 1.
+ *   4. Not soft: IsInShadow's one ray, origin p + N * RT_EPS, direction toC / distC, occluded iff the
+ *      any-hit traversal finds t < distC.  vis is 0 or 1; nothing is drawn.
+ *   5. Soft: W = (p - lpos) / distC, a = fabsf(W.x) > 0.9f ? (0,1,0) : (1,0,0), T = unit(cross(a, W)),
+ *      B = cross(W, T).  For i = 0 .. S-1: repeat x = 2 * rng_next(state) - 1, y = 2 * rng_next(state) - 1,
+ *      r2 = x*x + y*y until r2 > 1e-10f && r2 <= 1; lp = (lpos + T * (x * radius)) + B * (y * radius),
+ *      toL = lp - p, d = sqrtf(dot(toL, toL)); !(d > 0): the sample counts as unoccluded; otherwise
+ *      the ray from p + N * RT_EPS along toL / d with bound d, decided as in step 4.  Every sample is
+ *      cast (the count is the answer: no early out).  vis = float(unoccluded) / float(S).
+ *   After the last light rng_dev[id] = state: within a depth the lights' disk samples are drawn
+ *   first, then the bounce's xi (C/'s order).
+ *   An entry with tri < 0 or id RT_PATH_NONE gets a row of zeros, and no state word of it is read
+ *   or written.  vis_dev holds m * rt_scene_num_lights(s) floats, every one written.
+ *   shapes_dev: rt_scene_num_lights(s) records; they are copied back once per call (the call waits
+ *   for hip_stream up to that copy): a shadow_samples above RT_LIGHT_MAX_SHADOW_SAMPLES is
+ *   RT_ERR_UNSUPPORTED with no launch, and the largest S picks the lane mapping when lanes_per_entry
+ *   is 0.  lanes_per_entry: 0, or one of the built group sizes 1, 8, 32 (G lanes of a wave share an
+ *   entry and split each light's samples; the results do not depend on it); anything else is
+ *   RT_ERR_ARG.  flags: RT_FLAG_BINARY or 0; variant rule as for the queries, with a word of its
+ *   own (rt_light_visibility_variant).  hits_dev 16-byte aligned.  m == 0 or a scene without lights
+ *   is RT_OK with no launch; m > 2^31-1 is RT_ERR_UNSUPPORTED; every argument check runs before any
+ *   HIP call.  Ids unique and inside the state, as for the step.  The walk terminates for any bit
+ *   patterns (the LCG has full period, so the rejection loop ends; at most 256 * num_lights
+ *   traversals, each visiting a node at most once).  Results are specified for finite inputs.
+ *
+ * rt_path_step_vis_device: rt_path_step_device with one difference per light.  After the
+ *   NdotL > 0 test, v = vis_dev[k * num_lights + l]: !(v > 0) skips the light, otherwise
+ *   Lo += (radiance * f) * (NdotL * v) (C/'s form), which is the step's Lo += (radiance * f) * NdotL
+ *   bit for bit when v == 1.  With every shape a point light the two stages are therefore
+ *   rt_path_step_device, rt_shade_rays and the reference, bit for bit.  RT_PATH_NONE, RT_PATH_LAST,
+ *   mats_dev, direct_dev, the copy-through of dead entries and the argument rules are the step's; it
+ *   casts no ray (no variant; RT_FLAG_BINARY is accepted and has no meaning).
+ *
+ * rt_light_samples_host: the host build of everything of the visibility stage but the traversals,
+ *   through the functions the kernel runs.  For entry k and light l, rays[offsets[k * num_lights + l]
+ *   .. offsets[k * num_lights + l + 1]) are the shadow rays in cast order (a sample with !(d > 0)
+ *   casts none) and bounds[] their bounds; offsets holds m * num_lights + 1 words.  rays == NULL
+ *   writes the offsets alone and leaves rng as it is; otherwise cap is the room in rays and bounds
+ *   (too little: RT_ERR_ARG, nothing written but offsets) and rng is advanced as the stage does.
+ * rt_path_step_vis_host: rt_path_step_host with vis (floats) where that takes occluded (bytes).
+ * rt_host_scene_light_shapes: the shapes rt_host_scene_load_json read, one per light of
+ *   rt_scene_arrays::lights (optional keys "radius" and "shadow_samples" of a light; 0 and 1 when
+ *   absent; a key of another type than a number is RT_ERR_PARSE); cap: the room in out.
+ * (Additive to ABI 3: the names below.) */
+typedef struct { float radius; int32_t shadow_samples; } rt_light_shape;
+#define RT_LIGHT_MAX_SHADOW_SAMPLES 256
+int rt_scene_num_lights(const rt_scene* s);
+int rt_light_visibility_device(rt_scene* s, size_t m, const rt_hit* hits_dev, const uint32_t* ids_dev,
+                               const rt_light_shape* shapes_dev, uint32_t* rng_dev, int lanes_per_entry, int flags,
+                               float* vis_dev, void* hip_stream);
+int rt_light_visibility_variant(const rt_scene* s);
+int rt_path_step_vis_device(rt_scene* s, size_t m, const rt_ray* rays_dev, const rt_hit* hits_dev,
+                            const rt_material* mats_dev, const uint32_t* ids_dev, const float* vis_dev,
+                            const rt_path_opts* opt, const rt_path_state* st, rt_ray* next_rays_dev, uint8_t* alive_dev,
+                            float* direct_dev, void* hip_stream);
+int rt_light_samples_host(size_t m, const rt_hit* hits, const uint32_t* ids, const rt_light* lights,
+                          const rt_light_shape* shapes, int num_lights, uint32_t* rng, size_t cap, rt_ray* rays,
+                          float* bounds, uint64_t* offsets);
+int rt_path_step_vis_host(size_t m, const rt_ray* rays, const rt_hit* hits, const rt_material* mats, const uint32_t* ids,
+                          const rt_material* table, int num_table, const rt_light* lights, int num_lights,
+                          const float* vis, const rt_path_opts* opt, const rt_path_state* st, rt_ray* next_rays,
+                          uint8_t* alive, float* direct);
+int rt_host_scene_light_shapes(const rt_host_scene* s, rt_light_shape* out, int cap);
 
 /* ---- adaptive sampling: per-pixel sample counts, pixel-list rays and film ----------------------
  * Spending samples unevenly, exactly.  jittered_samples(k, 42) is a prefix of

@@ -35,6 +35,8 @@ RT_PATH_NONE = 0xFFFFFFFF
 RT_PIXEL_NONE = 0xFFFFFFFF
 RT_SORT_ORIGIN, RT_SORT_ORIGIN_DIR = 0, 1
 RT_MULTI_HIT_MAX_K = 32
+RT_LIGHT_MAX_SHADOW_SAMPLES = 256
+LIGHT_VIS_GROUPS = (1, 8, 32)  # the group sizes rt_light_visibility_device is built at (lanes_per_entry)
 # rt_tune_id (include/rt_mi355x.h): knob name -> id
 TUNE = {"frustum_arity": 0, "half_waves": 1, "paired_only": 2, "heavy_frac": 3, "heavy_cap": 4,
         "cull_coverage": 5, "cull_boxes": 6, "big_scene_bytes": 7, "frustum_stack_cap": 8,
@@ -270,6 +272,13 @@ SIGNATURES = {
     "rt_path_compact_scratch_bytes": (SZ, [SZ]),
     "rt_path_compact_device": (I, [I, SZ, P, P, P, P, P, P, P, P]),
     "rt_path_finish_device": (I, [I, SZ, P, P]),
+    "rt_scene_num_lights": (I, [P]),
+    "rt_light_visibility_device": (I, [P, SZ, P, P, P, P, I, I, P, P]),
+    "rt_light_visibility_variant": (I, [P]),
+    "rt_path_step_vis_device": (I, [P, SZ, P, P, P, P, P, P, P, P, P, P, P]),
+    "rt_light_samples_host": (I, [SZ, P, P, P, P, I, P, SZ, P, P, P]),
+    "rt_path_step_vis_host": (I, [SZ, P, P, P, P, P, I, P, I, P, P, P, P, P, P]),
+    "rt_host_scene_light_shapes": (I, [P, P, I]),
     "rt_camera_rays_pixels_host": (I, [P, P, SZ, P, I, P, I, P, P]),
     "rt_camera_rays_pixels_device": (I, [P, P, SZ, P, I, P, I, P, P, I, P]),
     "rt_afilm_create": (I, [I, I, I, P]),

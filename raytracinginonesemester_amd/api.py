@@ -29,6 +29,9 @@ from ._lib import check, lib, ptr
 
 LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("color", "<f4", 3), ("intensity", "<i4")])
 assert LIGHT_DTYPE.itemsize == C.sizeof(L.Light) == 28
+# rt_light_shape: a light's radius (<= 0 or NaN: a point light) and shadow rays per shaded point
+LIGHT_SHAPE_DTYPE = np.dtype([("radius", "<f4"), ("shadow_samples", "<i4")])
+assert LIGHT_SHAPE_DTYPE.itemsize == 8
 assert C.sizeof(L.Material) == 52 and C.sizeof(L.Triangle) == 72 and C.sizeof(L.AABB) == 24
 # rt_hit (include/rt_mi355x.h): one record of DeviceScene.trace_hits
 HIT_DTYPE = np.dtype([("tri", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("p", "<f4", 3), ("normal", "<f4", 3),
@@ -143,6 +146,9 @@ class HostScene:
         self.tri_object_ids = view(arr.tri_object_ids, np.int32, (P,))
         self.materials = view(arr.materials, np.float32, (info.num_materials, 13))
         self.lights = view(arr.lights, LIGHT_DTYPE, (info.num_lights,))
+        # the lights' shapes (the optional "radius" and "shadow_samples" of a light; point lights without)
+        self.light_shapes = np.zeros(info.num_lights, LIGHT_SHAPE_DTYPE)
+        check(lib().rt_host_scene_light_shapes(self._h, ptr(self.light_shapes), int(info.num_lights)))
         self.positions = view(arr.positions, np.float32, (nv, 3))
         self.normals = view(arr.normals, np.float32, (nv, 3))
         self.indices = view(arr.indices, np.uint32, (P, 3))
@@ -599,7 +605,7 @@ class DeviceScene:
     def render_rays(self, camera: Camera, spp: int, max_depth: int = 1, diffuse_bounce: bool = True,
                     miss_color=(0, 0, 0), jitter=None, pass_spp: Optional[int] = None,
                     band_rows: Optional[int] = None, ray_fn=None, p6: bool = False, film: Optional["Film"] = None,
-                    material_fn=None):
+                    material_fn=None, light_shapes=None):
         """A frame through the query path, on the device: for every sample pass (``pass_spp``
         samples; default all) and row band (``band_rows`` rows; default all) camera_rays ->
         ``ray_fn`` -> shade_rays -> Film.add, then one Film.resolve.  Memory is bounded by one
@@ -613,6 +619,8 @@ class DeviceScene:
         there stay in the sums); default a new one, closed on return.
         ``material_fn``: when given, the step's radiance comes from trace_paths with that hook (a
         material per hit; see trace_paths) instead of shade_rays.
+        ``light_shapes``: when given, the step's radiance comes from trace_paths with these shapes
+        (soft shadows where a radius is positive; see trace_paths).
         Returns Film.resolve's result for the whole image, on torch's current stream."""
         W, H, spp = camera.pixel_width, camera.pixel_height, int(spp)
         if spp < 1:
@@ -637,10 +645,11 @@ class DeviceScene:
                     rays, seeds = camera_rays(camera, n, jit[s0:s0 + n], r0, rows, device=self.device, sample0=s0)
                     if ray_fn is not None:
                         rays = ray_fn(rays, seeds, r0, rows, s0, n)
-                    if material_fn is None:
+                    if material_fn is None and light_shapes is None:
                         rad = self.shade_rays(rays, seeds, max_depth, diffuse_bounce, miss_color)
                     else:
-                        rad = self.trace_paths(rays, seeds, max_depth, diffuse_bounce, miss_color, material_fn=material_fn)
+                        rad = self.trace_paths(rays, seeds, max_depth, diffuse_bounce, miss_color, material_fn=material_fn,
+                                               light_shapes=light_shapes)
                     film.add(rad, r0, rows, n)
             return film.resolve(p6=p6)
         finally:
@@ -882,7 +891,7 @@ class DeviceScene:
 
     def path_step(self, rays, hits, state: "PathState", ids=None, materials=None, diffuse_bounce: bool = True,
                   miss_color=(0, 0, 0), flags: int = 0, last: bool = False, direct: bool = False, next_rays=None,
-                  stream: Optional[int] = None):
+                  stream: Optional[int] = None, vis=None):
         """One depth of TraceRayIterative's loop for ``m`` entries (rt_path_step_device): ``rays``
         (m, 6) float32 and ``hits`` (m, 16) int32, trace_hits' records or the caller's edits of
         them (tri, p, normal and material are read); entry k updates path ``ids[k]`` (int32 tensor,
@@ -895,7 +904,12 @@ class DeviceScene:
         entry, (m, 3)]: alive (m,) uint8 is 1 where the path goes on with next_rays[k]; a dead entry
         keeps its input ray.  ``next_rays`` may name the output tensor, ``rays`` itself included.
         With ``last`` (a path's last depth) there is no bounce and no draw, and (None, None) is
-        returned unless ``next_rays`` is given.  ``flags``: RT_FLAG_BINARY or 0."""
+        returned unless ``next_rays`` is given.  ``flags``: RT_FLAG_BINARY or 0.
+
+        ``vis``: light_visibility's (m, num_lights) float32 tensor.  With it the step casts no
+        shadow ray (rt_path_step_vis_device): a light with ``vis[k, l] <= 0`` is skipped and the
+        others' terms are scaled by it; ``vis`` of 1 where the shadow ray is clear and 0 where it is
+        not gives the plain step bit for bit."""
         import torch
 
         dev = self._torch_dev()
@@ -919,7 +933,18 @@ class DeviceScene:
             next_rays = torch.empty((m, 6), dtype=torch.float32, device=dev)
         alive = torch.empty(m, dtype=torch.uint8, device=dev) if want_out else None
         d = torch.empty((m, 3), dtype=torch.float32, device=dev) if direct else None
-        if m > 0:
+        if vis is not None:
+            if vis.device != dev or vis.dtype != torch.float32 or tuple(vis.shape) != (m, self.num_lights) or not vis.is_contiguous():
+                raise ValueError("path_step: vis must be the contiguous (m, num_lights) float32 tensor of light_visibility")
+            if m > 0:
+                o = L.PathOpts(1 if diffuse_bounce else 0, _v3(miss_color), int(flags) | (L.RT_PATH_LAST if last else 0))
+                check(lib().rt_path_step_vis_device(self._handle(), m, rays.data_ptr(), hits.data_ptr(),
+                                                    None if materials is None else materials.data_ptr(),
+                                                    None if ids is None else ids.data_ptr(), vis.data_ptr(), C.byref(o),
+                                                    C.byref(state.c), None if next_rays is None else next_rays.data_ptr(),
+                                                    None if alive is None else alive.data_ptr(),
+                                                    None if d is None else d.data_ptr(), _stream_of(stream, dev)))
+        elif m > 0:
             o = L.PathOpts(1 if diffuse_bounce else 0, _v3(miss_color), int(flags) | (L.RT_PATH_LAST if last else 0))
             check(lib().rt_path_step_device(self._handle(), m, rays.data_ptr(), hits.data_ptr(),
                                             None if materials is None else materials.data_ptr(),
@@ -933,8 +958,71 @@ class DeviceScene:
         """The traversal the latest path_step call launched for its shadow rays (RT_RAYS_VARIANT_*)."""
         return int(lib().rt_path_step_variant(self._handle()))
 
+    # ---- soft shadows: spherical area lights for the staged path (rt_light_visibility_*) --------
+    @property
+    def num_lights(self) -> int:
+        """The scene's light count (rt_scene_num_lights)."""
+        return int(lib().rt_scene_num_lights(self._handle()))
+
+    def _shape_tensor(self, light_shapes, who: str):
+        """light_shapes as the (num_lights, 2) int32 tensor of rt_light_shape records on the scene's
+        device: a LIGHT_SHAPE_DTYPE array (or anything np.asarray makes one of), such a tensor, or
+        None for point lights."""
+        import torch
+
+        dev, nl = self._torch_dev(), self.num_lights
+        if _is_torch(light_shapes):
+            if light_shapes.device != dev or light_shapes.dtype != torch.int32 or tuple(light_shapes.shape) != (nl, 2) \
+                    or not light_shapes.is_contiguous():
+                raise ValueError(f"{who}: a light_shapes tensor must be contiguous (num_lights, 2) int32 on {dev}")
+            return light_shapes
+        a = np.zeros(nl, LIGHT_SHAPE_DTYPE)
+        if light_shapes is None:
+            a["shadow_samples"] = 1
+        else:
+            b = np.ascontiguousarray(light_shapes, LIGHT_SHAPE_DTYPE).reshape(-1)
+            if b.shape != (nl,):
+                raise ValueError(f"{who}: light_shapes must hold one record per scene light")
+            a[:] = b
+        return torch.from_numpy(a.view(np.int32).reshape(nl, 2).copy()).to(dev)
+
+    def light_visibility(self, hits, state: "PathState", ids=None, light_shapes=None, lanes_per_entry: int = 0,
+                         flags: int = 0, stream: Optional[int] = None):
+        """The unoccluded fraction of every scene light at every hit (rt_light_visibility_device):
+        ``hits`` (m, 16) int32, trace_hits' records; entry k belongs to path ``ids[k]`` (None: k;
+        -1: no path) of ``state``, whose rng word the light's disk samples are drawn from and
+        which is advanced.  ``light_shapes``: one LIGHT_SHAPE_DTYPE record per light (array, or a
+        (num_lights, 2) int32 tensor of the same words); a radius <= 0 is a point light with one
+        shadow ray, None means that for all.  ``lanes_per_entry``: 0 (the library chooses) or one
+        of LIGHT_VIS_GROUPS; the result does not depend on it.  ``flags``: RT_FLAG_BINARY or 0.
+        Returns the (m, num_lights) float32 tensor path_step takes as ``vis``; a miss or an entry
+        without a path gets zeros.  The call reads the shapes back, which waits for the stream."""
+        import torch
+
+        dev = self._torch_dev()
+        if hits.device != dev or hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 16 or not hits.is_contiguous():
+            raise ValueError("light_visibility: hits must be the contiguous (m, 16) int32 tensor of trace_hits")
+        m = hits.shape[0]
+        if ids is not None and (ids.device != dev or ids.dtype != torch.int32 or tuple(ids.shape) != (m,) or not ids.is_contiguous()):
+            raise ValueError("light_visibility: ids must be a contiguous (m,) int32 tensor")
+        if ids is None and m > state.n:
+            raise ValueError("light_visibility: more entries than paths in the state")
+        sh = self._shape_tensor(light_shapes, "light_visibility")
+        nl = self.num_lights
+        vis = torch.empty((m, nl), dtype=torch.float32, device=dev)
+        st = _stream_of(stream, dev)
+        check(lib().rt_light_visibility_device(self._handle(), m, hits.data_ptr(), None if ids is None else ids.data_ptr(),
+                                               sh.data_ptr(), state.rng.data_ptr(), int(lanes_per_entry), int(flags),
+                                               vis.data_ptr(), st))
+        _used_on(st, dev, sh)
+        return vis
+
+    def light_visibility_variant(self) -> int:
+        """The traversal the latest light_visibility call launched (RT_RAYS_VARIANT_*)."""
+        return int(lib().rt_light_visibility_variant(self._handle()))
+
     def trace_paths(self, rays, seeds=None, max_depth: int = 1, diffuse_bounce: bool = True, miss_color=(0, 0, 0),
-                    material_fn=None, compact: bool = True, flags: int = 0, sort=None):
+                    material_fn=None, compact: bool = True, flags: int = 0, sort=None, light_shapes=None):
         """Radiance of caller rays by stages, on torch's current stream: path_begin, then per depth
         trace_hits -> ``material_fn`` -> path_step -> compact_paths, then path_finish.  With
         ``material_fn=None`` the result is shade_rays' bit for bit.
@@ -951,7 +1039,12 @@ class DeviceScene:
         trace_hits, after the compaction, the current rays and their ids are put into coherence
         order (``sort_rays`` in the scene's ``bounds()``; the ids become the order at the first
         depth).  Nothing is scattered back, the state being indexed by id; ``material_fn`` sees the
-        sorted entries with their ids.  The result is the same, bit for bit."""
+        sorted entries with their ids.  The result is the same, bit for bit.
+
+        ``light_shapes`` (one LIGHT_SHAPE_DTYPE record per light): when any radius is positive,
+        every depth runs trace_hits -> light_visibility -> path_step(vis=...): soft shadows from
+        spherical area lights, the disk samples drawn from each path's own rng before its bounce.
+        None, or shapes that are all point lights, leave the stages as they are."""
         import torch
 
         dev = self._torch_dev()
@@ -961,6 +1054,12 @@ class DeviceScene:
         if int(max_depth) <= 0 or n == 0:
             return torch.zeros((n, 3), dtype=torch.float32, device=dev)
         state = self.path_begin(n, seeds)
+        shapes = None
+        if light_shapes is not None:
+            sh_host = light_shapes.cpu().numpy().view(np.float32)[:, 0] if _is_torch(light_shapes) \
+                else np.ascontiguousarray(light_shapes, LIGHT_SHAPE_DTYPE).reshape(-1)["radius"]
+            if bool((sh_host > 0).any()):
+                shapes = self._shape_tensor(light_shapes, "trace_paths")
         cur, ids = rays.contiguous(), None
         if sort is False:
             sort = None
@@ -977,7 +1076,8 @@ class DeviceScene:
                 mats = material_fn(hits, cur, shown, depth)
                 if mats is not None:
                     mats = mats.to(dtype=torch.float32).contiguous()
-            nxt, alive = self.path_step(cur, hits, state, ids, mats, diffuse_bounce, miss_color, flags, last=last)
+            vis = None if shapes is None else self.light_visibility(hits, state, ids, shapes, flags=flags)
+            nxt, alive = self.path_step(cur, hits, state, ids, mats, diffuse_bounce, miss_color, flags, last=last, vis=vis)
             if last:
                 break
             if compact:
@@ -2124,6 +2224,73 @@ def path_step_host(rays, hits, radiance, throughput, rng, occluded, lights, tabl
         check(lib().rt_path_step_host(m, ptr(r), ptr(h), ptr(mt), ptr(idv), ptr(tb) if tb is not None and tb.size else None,
                                       0 if tb is None else tb.shape[0], ptr(lt) if lt.size else None, lt.size,
                                       ptr(occ) if occ.size else None, C.byref(o), C.byref(st), ptr(nxt), ptr(alive), ptr(direct)))
+    return nxt, alive, direct
+
+
+def _host_state(who: str, *arrays):
+    for a, dt in arrays:
+        if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError(f"{who}: the state must be writeable contiguous float32 / uint32 arrays")
+
+
+def light_samples_host(hits, lights, light_shapes, rng, ids=None):
+    """Host build of the visibility stage but for its traversals (rt_light_samples_host, no
+    device): ``hits`` (m,) HIT_DTYPE, ``lights`` LIGHT_DTYPE, ``light_shapes`` LIGHT_SHAPE_DTYPE,
+    ``rng`` (N,) uint32 advanced in place as the stage advances it, ``ids`` (m,) uint32 or None.
+    Returns ``(rays, bounds, offsets)``: the shadow rays (R, 6) float32 in cast order, their bounds
+    (R,) float32, and offsets (m * num_lights + 1,) uint64 with entry k's rays to light l at
+    ``offsets[k * num_lights + l] : offsets[k * num_lights + l + 1]``."""
+    h = np.ascontiguousarray(hits, HIT_DTYPE)
+    m = h.shape[0]
+    lt = np.ascontiguousarray(lights, LIGHT_DTYPE).reshape(-1)
+    sh = np.ascontiguousarray(light_shapes, LIGHT_SHAPE_DTYPE).reshape(-1)
+    idv = None if ids is None else _c(ids, np.uint32)
+    _host_state("light_samples_host", (rng, np.uint32))
+    if h.shape != (m,) or sh.shape != lt.shape or (idv is not None and idv.shape != (m,)):
+        raise ValueError("light_samples_host: the arrays do not match the batch")
+    used = idv[idv != L.RT_PATH_NONE] if idv is not None else np.arange(m)
+    if used.size and int(used.max()) >= rng.shape[0]:
+        raise ValueError("light_samples_host: a path id outside the state")
+    off = np.zeros(m * lt.size + 1, np.uint64)
+    args = (m, ptr(h) if m else None, ptr(idv), ptr(lt) if lt.size else None, ptr(sh) if lt.size else None, lt.size,
+            ptr(rng) if m else None)
+    check(lib().rt_light_samples_host(*args, 0, None, None, ptr(off)))
+    total = int(off[-1])
+    rays, bounds = np.zeros((total, 6), np.float32), np.zeros(total, np.float32)
+    if total:
+        check(lib().rt_light_samples_host(*args, total, ptr(rays), ptr(bounds), ptr(off)))
+    return rays, bounds, off
+
+
+def path_step_vis_host(rays, hits, radiance, throughput, rng, vis, lights, table=None, materials=None, ids=None,
+                       diffuse_bounce: bool = True, miss_color=(0, 0, 0), last: bool = False):
+    """path_step_host with ``vis`` (m, num_lights) float32, light_visibility's values, where that
+    takes ``occluded`` (rt_path_step_vis_host).  Returns ``(next_rays, alive, direct)``."""
+    r = _c(rays, np.float32)
+    m = r.shape[0]
+    h = np.ascontiguousarray(hits, HIT_DTYPE)
+    lt = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    vs = _c(vis, np.float32).reshape(m, lt.size)
+    tb = None if table is None else _c(table, np.float32).reshape(-1, 13)
+    mt = None if materials is None else _c(materials, np.float32)
+    idv = None if ids is None else _c(ids, np.uint32)
+    _host_state("path_step_vis_host", (radiance, np.float32), (throughput, np.float32), (rng, np.uint32))
+    N = rng.shape[0]
+    if r.shape != (m, 6) or h.shape != (m,) or radiance.shape != (N, 3) or throughput.shape != (N, 3) \
+            or (mt is not None and mt.shape != (m, 13)) or (idv is not None and idv.shape != (m,)):
+        raise ValueError("path_step_vis_host: the arrays do not match the batch")
+    used = idv[idv != L.RT_PATH_NONE] if idv is not None else np.arange(m)
+    if used.size and int(used.max()) >= N:
+        raise ValueError("path_step_vis_host: a path id outside the state")
+    nxt = np.zeros((m, 6), np.float32)
+    alive = np.zeros(m, np.uint8)
+    direct = np.zeros((m, 3), np.float32)
+    st = L.PathStateT(ptr(radiance), ptr(throughput), ptr(rng))
+    o = L.PathOpts(1 if diffuse_bounce else 0, _v3(miss_color), L.RT_PATH_LAST if last else 0)
+    if m > 0:
+        check(lib().rt_path_step_vis_host(m, ptr(r), ptr(h), ptr(mt), ptr(idv), ptr(tb) if tb is not None and tb.size else None,
+                                          0 if tb is None else tb.shape[0], ptr(lt) if lt.size else None, lt.size,
+                                          ptr(vs) if vs.size else None, C.byref(o), C.byref(st), ptr(nxt), ptr(alive), ptr(direct)))
     return nxt, alive, direct
 
 

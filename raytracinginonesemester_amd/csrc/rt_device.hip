@@ -38,12 +38,14 @@
 //   rt_multihit.hpp    multi-hit queries (rt_trace_multi_hits*)
 //   rt_closest.hpp     closest-point queries (rt_closest_points*)
 //   rt_path.hpp        path stages for caller hits (rt_path_*): step, begin, compaction, finish
+//   rt_softshadow.hpp  spherical area lights for the staged path (rt_light_visibility_*, rt_path_step_vis_*)
 //   rt_refit.hpp       refit of a resident scene for deforming geometry (rt_scene_refit*), mesh -> triangles
 //   rt_rebuild.hpp     rebuild of a resident scene (rt_scene_rebuild*): the record weight on the device
 //   rt_scan.hpp        the compaction's scan of tile counts (through rt_path.hpp; also used by rt_frame.hip)
 // The host side of the caller queries is a section too, included after rt_scene and scene_view:
 //   rt_query_host.hpp  rt_trace_rays*, rt_shade_rays*, rt_trace_hits*, rt_trace_multi_hits*, rt_closest_points*,
-//                      rt_camera_rays*, rt_path_*: checks, launches, staged forms, host builds
+//                      rt_camera_rays*, rt_path_*, rt_light_*: checks, launches, staged forms, host builds
+//                      
 // Separate translation units: rt_scene_pack.cpp (the host half of rt_scene_create: checks, ids,
 // stack bounds, every packed array), rt_records.cpp (host record builders), rt_hw1.hip (the HW1
 // path), rt_frame.hip, rt_lbvh.hip, rt_renderer.hip.
@@ -209,6 +211,7 @@ static_assert(sizeof(RenderParams) == 544, "RenderParams: a field moved");
 #include "rt_multihit.hpp"
 #include "rt_closest.hpp"
 #include "rt_path.hpp"
+#include "rt_softshadow.hpp"
 #include "rt_refit.hpp"
 #include "rt_rebuild.hpp"
 
@@ -806,7 +809,7 @@ using rt::KernelTimer;
 using rt::Staging;
 
 // The caller-query families (rt_query_host.hpp): each has a variant word of its own on the scene.
-enum QueryKind { kTraceRays, kShadeRays, kTraceHits, kPathStep, kMultiHits, kClosestPoints, kQueryKinds };
+enum QueryKind { kTraceRays, kShadeRays, kTraceHits, kPathStep, kMultiHits, kClosestPoints, kLightVis, kQueryKinds };
 static_assert(RT_RAYS_VARIANT_NONE == 0, "rt_scene::variant starts zeroed");
 
 // The scene's two frame streams (rt_scene::rstream) at the pre-pass stream's high priority (0,

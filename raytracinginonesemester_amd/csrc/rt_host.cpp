@@ -589,6 +589,7 @@ struct SceneDesc {
     double focal_mm = 50.0, sensor_mm = 24.0;
     int width = 100, height = 100;
     std::vector<rt_light> lights;
+    std::vector<rt_light_shape> shapes;  // one per light (C/'s two more keys of a light)
     std::vector<SceneObject> objects;
 };
 
@@ -607,6 +608,22 @@ bool read_light(const Json& item, rt_light& lc) {  // scene.h:307-316, 322-330
     const Json* v = item.get("intensity");
     if (v && v->type == Json::Number) lc.intensity = json_int(v->num);
     return true;
+}
+
+// The light's shape, C/'s `radius` and `shadow_samples` (C/include/scene.h): a point light, 0 and
+// 1, when absent.  A key that is there with another type than a number is an error.
+int read_light_shape(const Json& item, rt_light_shape& sh) {
+    sh.radius = 0.0f;
+    sh.shadow_samples = 1;
+    if (const Json* v = item.get("radius")) {
+        if (v->type != Json::Number) return set_error(RT_ERR_PARSE, "light: 'radius' is not a number");
+        sh.radius = float(v->num);
+    }
+    if (const Json* v = item.get("shadow_samples")) {
+        if (v->type != Json::Number) return set_error(RT_ERR_PARSE, "light: 'shadow_samples' is not a number");
+        sh.shadow_samples = json_int(v->num);
+    }
+    return RT_OK;
 }
 
 // G/include/scene.h:242-380
@@ -636,19 +653,26 @@ int parse_scene(const Json& root, SceneDesc& sc) {
         if (sc.height < 1) sc.height = 1;
     }
     sc.lights.clear();
+    sc.shapes.clear();
     if (const Json* ls = root.get("lights"); ls && ls->type == Json::Array) {
         for (const auto& item : ls->arr) {
             if (item.type != Json::Object) continue;
             rt_light lc;
+            rt_light_shape sh;
             read_light(item, lc);
+            if (const int rc = read_light_shape(item, sh); rc != RT_OK) return rc;
             sc.lights.push_back(lc);
+            sc.shapes.push_back(sh);
         }
     }
     if (sc.lights.empty()) {
         if (const Json* l = root.get("light"); l && l->type == Json::Object) {
             rt_light lc;
+            rt_light_shape sh;
             read_light(*l, lc);
+            if (const int rc = read_light_shape(*l, sh); rc != RT_OK) return rc;
             sc.lights.push_back(lc);
+            sc.shapes.push_back(sh);
         }
     }
     const Json* arr = root.get("scene");
@@ -879,6 +903,7 @@ struct rt_host_scene {
     Mesh mesh;
     std::vector<rt_material> materials;
     std::vector<rt_light> lights;
+    std::vector<rt_light_shape> shapes;  // one per light (rt_host_scene_light_shapes)
     std::vector<rt_bvh_node> nodes;
     std::vector<rt_aabb> aabbs;
     std::vector<rt_triangle> tris;
@@ -945,6 +970,8 @@ int finish_scene(rt_host_scene* hs) {
         l.intensity = 1;
         hs->lights.push_back(l);
     }
+    hs->shapes = hs->desc.shapes;
+    hs->shapes.resize(hs->lights.size(), rt_light_shape{0.0f, 1});  // (the fallback light, rt_host_scene_load_objs)
     tree_stats(hs->nodes, hs->max_stack, hs->height);
     return RT_OK;
 }
@@ -1066,6 +1093,13 @@ extern "C" int rt_host_scene_arrays(const rt_host_scene* s, rt_scene_arrays* o) 
     o->positions = s->mesh.positions.data();
     o->normals = s->mesh.normals.empty() ? nullptr : s->mesh.normals.data();
     o->indices = s->mesh.indices.data();
+    return RT_OK;
+}
+
+extern "C" int rt_host_scene_light_shapes(const rt_host_scene* s, rt_light_shape* out, int cap) {
+    if (!s || cap < 0 || (cap > 0 && !out)) return set_error(RT_ERR_ARG, "rt_host_scene_light_shapes: null argument");
+    if (size_t(cap) < s->shapes.size()) return set_error(RT_ERR_ARG, "rt_host_scene_light_shapes: room for fewer shapes than lights");
+    std::copy(s->shapes.begin(), s->shapes.end(), out);
     return RT_OK;
 }
 

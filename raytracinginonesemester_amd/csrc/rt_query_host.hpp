@@ -801,3 +801,220 @@ extern "C" int rt_path_compact_device(int device, size_t m, const uint8_t* alive
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
+
+// ---- spherical area lights for the staged path (rt_softshadow.hpp) ------------------------------
+static_assert(sizeof(DevLightShape) == sizeof(rt_light_shape) && sizeof(rt_light_shape) == 8, "rt_light_shape");
+static_assert(SOFT_MAX_SAMPLES == RT_LIGHT_MAX_SHADOW_SAMPLES, "RT_LIGHT_MAX_SHADOW_SAMPLES");
+
+extern "C" int rt_scene_num_lights(const rt_scene* s) {
+    return s ? s->nlights : 0;
+}
+
+namespace {
+// The group sizes light_visibility_kernel is built at.
+constexpr bool light_vis_built(int g) { return g == 1 || g == 8 || g == 32; }
+
+// lanes_per_entry == 0: the group size for a launch whose largest light takes smax rays per
+// entry: the largest built size that smax fills.  DESIGN.md §4.30's table
+// (profiles/r14/soft_shadows.jsonl): at S = 1 a group of 8 or 32 costs 1.6x and 1.7x one lane per
+// entry, at S = 8 one lane costs 2.2x a group of 8, at S = 32 and 128 a group of 8 costs 2.7x and
+// 3.0x a group of 32.  The batch size is not part of the rule: one m was measured.
+int light_vis_group(int smax) {
+    if (smax >= 32) return 32;
+    if (smax >= 8) return 8;
+    return 1;
+}
+
+// No HIP call and no read through any pointer but s before the checks pass.
+int light_vis_args(const rt_scene* s, size_t m, const void* hits, const void* ids, const void* shapes, const void* rng,
+                   int lanes_per_entry, int flags, const void* vis) {
+    if (!s) return set_error(RT_ERR_ARG, "rt_light_visibility_device: null scene");
+    if (flags & ~RT_FLAG_BINARY) return set_error(RT_ERR_ARG, "rt_light_visibility_device: unknown flag");
+    if (lanes_per_entry != 0 && !light_vis_built(lanes_per_entry))
+        return set_error(RT_ERR_ARG, "rt_light_visibility_device: lanes_per_entry is not 0, 1, 8 or 32");
+    if (m > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_light_visibility_device: more than 2^31-1 entries in one batch");
+    if (m == 0 || s->nlights == 0) return RT_OK;
+    if (!hits || !shapes || !rng || !vis) return set_error(RT_ERR_ARG, "rt_light_visibility_device: null hits, shapes, rng or vis");
+    if (reinterpret_cast<uintptr_t>(hits) % 16 != 0) return set_error(RT_ERR_ARG, "rt_light_visibility_device: hits_dev is not 16-byte aligned");
+    for (const void* p : {ids, shapes, rng, vis})
+        if (reinterpret_cast<uintptr_t>(p) % 4 != 0) return set_error(RT_ERR_ARG, "rt_light_visibility_device: ids, shapes, rng or vis is not 4-byte aligned");
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_light_visibility_device(rt_scene* s, size_t m, const rt_hit* hits, const uint32_t* ids,
+                                          const rt_light_shape* shapes, uint32_t* rng, int lanes_per_entry, int flags,
+                                          float* vis, void* stream) {
+    int rc = light_vis_args(s, m, hits, ids, shapes, rng, lanes_per_entry, flags, vis);
+    if (rc != RT_OK || m == 0 || s->nlights == 0) return rc;
+    DeviceGuard g(s->device);
+    if ((rc = deep_has_tris(s, "rt_light_visibility_device")) != RT_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // The shapes decide an error (too many samples) and the group size: one small copy back, in
+    // stream order after whatever wrote them.
+    std::vector<rt_light_shape> sh(size_t(s->nlights));
+    HIP_TRY(hipMemcpyAsync(sh.data(), shapes, sh.size() * sizeof(rt_light_shape), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int smax = 1;
+    for (const rt_light_shape& x : sh) {
+        if (x.shadow_samples > SOFT_MAX_SAMPLES)
+            return set_error(RT_ERR_UNSUPPORTED, "rt_light_visibility_device: shadow_samples above RT_LIGHT_MAX_SHADOW_SAMPLES");
+        if (x.radius > 0.0f) smax = std::max(smax, x.shadow_samples);
+    }
+    const int G = lanes_per_entry != 0 ? lanes_per_entry : light_vis_group(smax);
+    const int variant = s->query_variant(flags);
+    LightVisParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.sc = query_view(s, variant);  // (the packed records of the shadow rays and the lights)
+    P.hits = reinterpret_cast<const uint4*>(hits);
+    P.ids = ids;
+    P.shapes = reinterpret_cast<const DevLightShape*>(shapes);
+    P.rng = rng;
+    P.vis = vis;
+    P.m = uint32_t(m);
+    const unsigned long long lanes = (unsigned long long)m * (unsigned long long)G;  // < 2^36
+    const dim3 grid((unsigned)((lanes + BLOCK - 1) / BLOCK)), block(BLOCK);
+    return launch_variant(s, kLightVis, variant, [&](auto V) {
+        if (G == 1) hipLaunchKernelGGL((light_visibility_kernel<V(), 1>), grid, block, 0, st, P);
+        else if (G == 8) hipLaunchKernelGGL((light_visibility_kernel<V(), 8>), grid, block, 0, st, P);
+        else hipLaunchKernelGGL((light_visibility_kernel<V(), 32>), grid, block, 0, st, P);
+    });
+}
+
+extern "C" int rt_light_visibility_variant(const rt_scene* s) {
+    return variant_of(s, kLightVis);
+}
+
+extern "C" int rt_path_step_vis_device(rt_scene* s, size_t m, const rt_ray* rays, const rt_hit* hits, const rt_material* mats,
+                                       const uint32_t* ids, const float* vis, const rt_path_opts* opt,
+                                       const rt_path_state* state, rt_ray* next, uint8_t* alive, float* direct, void* stream) {
+    if (!s) return set_error(RT_ERR_ARG, "rt_path_step_vis_device: null scene");
+    int rc = path_step_args("rt_path_step_vis_device", m, rays, hits, opt, state, next, alive, RT_FLAG_BINARY | RT_PATH_LAST);
+    if (rc != RT_OK) return rc;
+    if (s->nlights > 0 && !vis) return set_error(RT_ERR_ARG, "rt_path_step_vis_device: null vis");
+    // the kernel loads 16-byte words
+    if (reinterpret_cast<uintptr_t>(hits) % 16 != 0) return set_error(RT_ERR_ARG, "rt_path_step_vis_device: hits_dev is not 16-byte aligned");
+    if (m == 0) return RT_OK;
+    DeviceGuard g(s->device);
+    const SceneView v = scene_view(s);
+    PathStepVisParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.rays = reinterpret_cast<const float*>(rays);
+    P.hits = reinterpret_cast<const uint4*>(hits);
+    P.mats = reinterpret_cast<const float*>(mats);
+    P.ids = ids;
+    P.vis = vis;
+    P.table = v.mats;
+    P.lights = v.lights;
+    P.num_table = v.num_mats;
+    P.num_lights = v.num_lights;
+    P.m = uint32_t(m);
+    P.diffuse_bounce = opt->diffuse_bounce;
+    P.last = (opt->flags & RT_PATH_LAST) ? 1 : 0;
+    P.miss = mk(opt->miss_color.x, opt->miss_color.y, opt->miss_color.z);
+    P.radiance = state->radiance;
+    P.throughput = state->throughput;
+    P.rng = state->rng;
+    P.next = P.last && !next ? nullptr : reinterpret_cast<float*>(next);
+    P.alive = alive;
+    P.direct = direct;
+    hipLaunchKernelGGL(path_step_vis_kernel, dim3((P.m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// The host build of the visibility stage but for its traversals: per entry and light, in cast
+// order, the shadow rays and their bounds through the functions the kernel runs.
+extern "C" int rt_light_samples_host(size_t m, const rt_hit* hits, const uint32_t* ids, const rt_light* lights,
+                                     const rt_light_shape* shapes, int num_lights, uint32_t* rng, size_t cap, rt_ray* rays,
+                                     float* bounds, uint64_t* offsets) {
+    if (m > 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_light_samples_host: more than 2^31-1 entries in one batch");
+    if (num_lights < 0 || !offsets || (m > 0 && (!hits || !rng)) || (num_lights > 0 && (!lights || !shapes)) || (rays && !bounds))
+        return set_error(RT_ERR_ARG, "rt_light_samples_host: null hits, rng, lights, shapes, bounds or offsets");
+    for (int l = 0; l < num_lights; ++l)
+        if (shapes[l].shadow_samples > SOFT_MAX_SAMPLES)
+            return set_error(RT_ERR_UNSUPPORTED, "rt_light_samples_host: shadow_samples above RT_LIGHT_MAX_SHADOW_SAMPLES");
+    const DevLight* L = reinterpret_cast<const DevLight*>(lights);
+    // write: store the rays and advance the rng; else count only, on copies of the state words
+    auto pass = [&](bool write) {
+        uint64_t n = 0;
+        for (size_t k = 0; k < m; ++k) {
+            const uint32_t id = ids ? ids[k] : uint32_t(k);
+            HitWords h;  // (the caller's records need no alignment)
+            std::memcpy(&h, hits + k, sizeof(h));
+            const bool skip = id == PATH_NONE || (int32_t)h.w[0].x < 0;
+            const f3 p = mk(pw::asf(h.w[1].x), pw::asf(h.w[1].y), pw::asf(h.w[1].z));
+            const f3 N = skip ? p : unit(mk(pw::asf(h.w[1].w), pw::asf(h.w[2].x), pw::asf(h.w[2].y)));
+            const f3 origin = add(p, scale(N, RT_EPS));
+            uint32_t state = skip ? 0u : rng[id];
+            auto emit = [&](f3 dir, float d) {
+                if (write) {
+                    rays[n].origin = rt_vec3{origin.x, origin.y, origin.z};
+                    rays[n].direction = rt_vec3{dir.x, dir.y, dir.z};
+                    bounds[n] = d;
+                }
+                ++n;
+            };
+            for (int l = 0; l < num_lights; ++l) {
+                offsets[k * size_t(num_lights) + size_t(l)] = n;
+                if (skip) continue;
+                const f3 lpos = mk(L[l].pos[0], L[l].pos[1], L[l].pos[2]);
+                const DevLightShape shape = {shapes[l].radius, shapes[l].shadow_samples};
+                f3 toC;
+                float distC;
+                int S;
+                const SoftClass cls = soft_class(p, N, lpos, shape, toC, distC, S);
+                if (cls == SOFT_POINT) emit(divf(toC, distC), distC);
+                if (cls != SOFT_DISK) continue;
+                f3 T, B;
+                soft_basis(p, lpos, distC, T, B);
+                for (int i = 0; i < S; ++i) {
+                    float x, y, d;
+                    f3 dir;
+                    soft_disk_draw(state, x, y);
+                    if (soft_sample_ray(p, lpos, T, B, shape.radius, x, y, dir, d)) emit(dir, d);
+                }
+            }
+            if (write && !skip) rng[id] = state;
+        }
+        offsets[m * size_t(num_lights)] = n;
+        return n;
+    };
+    const uint64_t total = pass(false);
+    if (!rays) return RT_OK;
+    if (total > cap) return set_error(RT_ERR_ARG, "rt_light_samples_host: room for fewer rays than the batch casts");
+    pass(true);
+    return RT_OK;
+}
+
+// The host build of the step with visibilities: path_step_vis_one as path_step_vis_kernel runs it.
+extern "C" int rt_path_step_vis_host(size_t m, const rt_ray* rays, const rt_hit* hits, const rt_material* mats,
+                                     const uint32_t* ids, const rt_material* table, int num_table, const rt_light* lights,
+                                     int num_lights, const float* vis, const rt_path_opts* opt, const rt_path_state* state,
+                                     rt_ray* next, uint8_t* alive, float* direct) {
+    const int rc = path_step_args("rt_path_step_vis_host", m, rays, hits, opt, state, next, alive, RT_FLAG_BINARY | RT_PATH_LAST);
+    if (rc != RT_OK) return rc;
+    if (num_table < 0 || num_lights < 0 || (num_table > 0 && !table) || (num_lights > 0 && (!lights || !vis)))
+        return set_error(RT_ERR_ARG, "rt_path_step_vis_host: a table, light set or visibility array that does not match its count");
+    const bool last = (opt->flags & RT_PATH_LAST) != 0;
+    const f3 miss = mk(opt->miss_color.x, opt->miss_color.y, opt->miss_color.z);
+    for (size_t k = 0; k < m; ++k) {
+        const float* R = reinterpret_cast<const float*>(rays + k);
+        float* nx = next ? reinterpret_cast<float*>(next + k) : nullptr;
+        const uint32_t id = ids ? ids[k] : uint32_t(k);
+        if (id == PATH_NONE) {
+            if (nx) std::memmove(nx, R, sizeof(rt_ray));
+            if (alive) alive[k] = 0;
+            if (direct) direct[3 * k] = direct[3 * k + 1] = direct[3 * k + 2] = 0.0f;
+            continue;
+        }
+        HitWords h;  // (the caller's records need no alignment)
+        std::memcpy(&h, hits + k, sizeof(h));
+        path_step_vis_one(R, h.w, mats ? reinterpret_cast<const float*>(mats + k) : nullptr,
+                          reinterpret_cast<const DevMaterial*>(table), num_table, reinterpret_cast<const DevLight*>(lights),
+                          num_lights, vis + k * size_t(num_lights), miss, opt->diffuse_bounce != 0, last,
+                          state->radiance + 3 * size_t(id), state->throughput + 3 * size_t(id), state->rng + id, nx,
+                          alive ? alive + k : nullptr, direct ? direct + 3 * k : nullptr);
+    }
+    return RT_OK;
+}
